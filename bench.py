@@ -7,6 +7,12 @@ camera already resident in HBM, plus - for N > 1 - the RCCL gather of every
 rank's tile-packed slab to rank 0 and its unpack into the frame. Rank 0 prints
 one JSON line.
 
+A plain run sets up, warms up, times `--steps` steps (`ms_per_step`, `value`),
+writes the last timed frame with `--dump-outputs DIR` and prints the line. `--full`
+adds what takes runs of its own: the work-counting launch, the dominant kernel's
+time and roofline, the oracle parity rows of the timed frame, the CPU baseline, and
+three timed repeats (the median reported) in place of one.
+
 `python bench.py --gpus N` with N > 1 starts torch.distributed.run (one process
 per GPU) as a child process before touching the GPU and forwards rank 0's line
 and the exit code; under torch.distributed.run, WORLD_SIZE must equal --gpus.
@@ -165,8 +171,16 @@ def parse_args(argv):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="timed repeats of --steps steps; the median repeat is reported (SURVEY.md §8d)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of --steps steps, the median repeat reported (SURVEY.md §8d); default: 1, "
+                         "so --steps is the number of timed steps, and 3 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the work-counting launch, the dominant kernel's "
+                         "time and roofline, the oracle parity rows of the timed frame and the CPU baseline "
+                         "(each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy: "
+                         "frame.npy, the u8 frame as it reached host memory, stored as float32 (H, W, 3)")
     ap.add_argument("--scene", default="cornell", choices=sorted(SCENES))
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--spp", type=int, default=256)
@@ -194,9 +208,33 @@ def parse_args(argv):
                     help="--single-process: comma-separated device ordinals (default 0..N-1; a repeated ordinal "
                          "rehearses the N-way split on fewer GPUs)")
     a = ap.parse_args(argv)
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
     if a.repeats < 1 or a.steps < 1 or a.warmup < 0 or a.gpus < 1:
         ap.error("--repeats and --steps must be >= 1, --warmup >= 0, --gpus >= 1")
     return a
+
+
+DUMP_MAX_PIXELS = 1 << 21  # 2 Mi pixels: 24 MiB of float32 RGB + 16 MiB of float64 indices, under 64 MB
+
+
+def dump_outputs(out_dir: str, frame_u8) -> None:
+    """--dump-outputs: the last timed step's result, the u8 frame in host memory, as
+    DIR/frame.npy (float32, the u8 values unchanged). A frame of more than DUMP_MAX_PIXELS
+    pixels is sampled: frame.npy holds the pixels whose flat indices (j * W + i, ascending,
+    drawn once from a fixed seed) are in frame_index.npy (float64, exact below 2^53)."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    H, W = frame_u8.shape[:2]
+    if H * W <= DUMP_MAX_PIXELS:
+        np.save(d / "frame.npy", frame_u8.astype(np.float32))
+    else:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(H * W, DUMP_MAX_PIXELS, replace=False))
+        np.save(d / "frame.npy", frame_u8.reshape(H * W, 3)[idx].astype(np.float32))
+        np.save(d / "frame_index.npy", idx.astype(np.float64))
+    log(f"outputs of the last timed step written to {d}")
 
 
 def _load_profile(name: str, key: str):
@@ -332,7 +370,7 @@ def main(argv=None):
     # on min(spp, 64) samples and, for large scenes, a 1/count_sub tile subsample.
     counters = None
     sub = args.count_sub or (16 if cam.info["n_objects"] > 1000 else 1)
-    if not args.no_count:
+    if args.full and not args.no_count:
         spp_c = min(args.spp, 64)
         cam_c = rt.create_camera_from_scene_data(scene_data, {**ropts, "samples": spp_c})
         st_c, counters = cam_c.render_device(rgb_ptr=frame.data_ptr(), tile_group=rank, tile_groups=world * sub,
@@ -369,10 +407,12 @@ def main(argv=None):
                 host_frames[b].copy_(fr, non_blocking=True)  # D2H inside the timed step
             copied[b].record(copy_stream)
 
-    # this rank's share (untimed): pixels and samples per launch
-    st, _ = cam.render_device(rgb_ptr=frame.data_ptr(), tile_group=rank, tile_groups=world, stream=sptr,
-                              synchronize=True)
-    my_pixels, my_samples = int(st.pixels), int(st.samples["total"])
+    # --full: this rank's share (untimed), pixels and samples per launch, for the roofline
+    my_pixels = my_samples = 0
+    if args.full:
+        st, _ = cam.render_device(rgb_ptr=frame.data_ptr(), tile_group=rank, tile_groups=world, stream=sptr,
+                                  synchronize=True)
+        my_pixels, my_samples = int(st.pixels), int(st.samples["total"])
     if counters:
         scale = my_samples / max(counters["samples"], 1)
         counters = {k: v * scale for k, v in counters.items()}
@@ -380,7 +420,7 @@ def main(argv=None):
         step()
         torch.cuda.synchronize()
         log(f"warmup {i + 1}/{args.warmup}")
-    # three repeats, the median reported. Each repeat times exactly `steps`
+    # Each repeat (one; SURVEY.md §8d's three with --full, the median reported) times exactly `steps`
     # steps between a barrier + synchronize on both sides; the max over ranks is taken per repeat.
     reps = []
     for r in range(args.repeats):
@@ -397,18 +437,22 @@ def main(argv=None):
             dist.barrier()
         reps.append(time.perf_counter() - t0)
 
-    # Kernel time of the dominant kernel, from HIP events the library records on
+    timed_rgb = host_frames[(nstep[0] - 1) % 2].numpy().copy() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_rgb)
+
+    # --full: kernel time of the dominant kernel, from HIP events the library records on
     # the launch stream (per pass, path kernel and accumulate separately), over
     # untimed renders of this rank's share after the timed region.
     kt = []
-    for _ in range(max(3, min(args.steps, 10))):
+    for _ in range(max(3, min(args.steps, 10)) if args.full else 0):
         cam.render_device(rgb_ptr=(slab if world > 1 else frame).data_ptr(), tile_group=rank, tile_groups=world,
                           stream=sptr, packed=world > 1)
         kt.append(cam.kernel_times())
     passes = cam.pass_count()
     a_rounds, a_rendered = cam.adaptive_info()
-    kernel_ms = sum(a for a, _ in kt) / len(kt)
-    accum_ms = sum(b for _, b in kt) / len(kt)
+    kernel_ms = sum(a for a, _ in kt) / max(len(kt), 1)
+    accum_ms = sum(b for _, b in kt) / max(len(kt), 1)
     kind = cam.last_kernel()  # the path kernel the library launched (rt_camera_last_kernel)
     kernel_name = {"pool": "pt_pool_kernel", "chunked": "pt_chunk_kernel"}.get(kind, "pt_render_kernel")
 
@@ -418,10 +462,10 @@ def main(argv=None):
     reps = [float(x) for x in t[:len(reps)]]
     elapsed = sorted(reps)[len(reps) // 2]  # the median repeat (max over ranks)
 
-    # Untimed: the same frame again with its fp32 radiance (assembled over the ranks
-    # like the timed frames) and the merged RenderStats, for the checks below.
-    radiance = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-    timed_rgb = host_frames[(nstep[0] - 1) % 2].numpy().copy() if rank == 0 else None
+    # Untimed: the same frame again (assembled over the ranks like the timed frames) for the
+    # merged RenderStats, the samples a step traces; with --full also its fp32 radiance, for
+    # the checks below.
+    radiance = torch.zeros((H, W, 3), dtype=torch.float32, device=dev) if args.full else None
     res = rtd.render_frame(cam, frame, rank, world, stream=sptr, radiance=radiance, stats=True)
     torch.cuda.synchronize()
     frame_check = None
@@ -432,7 +476,7 @@ def main(argv=None):
             frame_check = bool(torch.equal(single, frame)) and _stats_equal(res[1], st1)
             log(f"frame check (assembled frame and merged stats == single launch): {frame_check}")
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         parity = parity_check(scene_data, ropts, args, timed_rgb, frame.cpu().numpy(), radiance.cpu().numpy(),
                               res[1])
     if world > 1:
@@ -445,10 +489,11 @@ def main(argv=None):
         value = samples_per_step * args.steps / elapsed / 1e6
         key = f"{args.scene}_{W}x{H}_spp{args.spp}_d{args.depth}_{args.precision}_n{world}" + \
             ("_adaptive" if args.adaptive else "")
-        rl = roofline(key, rt.build_id(), my_samples, kernel_ms, counters, my_pixels)
-        rl.update({"kernel": kernel_name, "accum_kernel_ms": round(accum_ms, 4), "passes": passes,
-                   "count_subsample": sub})
-        if accum_ms > 0 and not args.adaptive:
+        rl = roofline(key, rt.build_id(), my_samples, kernel_ms, counters, my_pixels) if args.full else None
+        if rl is not None:
+            rl.update({"kernel": kernel_name, "accum_kernel_ms": round(accum_ms, 4), "passes": passes,
+                       "count_subsample": sub})
+        if rl is not None and accum_ms > 0 and not args.adaptive:
             # the in-order accumulate pass (pt_accum_kernel) is the HBM-bound kernel of the frame: it
             # streams every sample's record (12 B {r, g, b} at fixed spp in colour mode, 16 B with
             # the bounce word) once and writes each pixel's u8 RGB (3 B); algorithmic bytes / its time
@@ -458,12 +503,12 @@ def main(argv=None):
             rl["accumulate"] = {"kernel": "pt_accum_kernel", "bound": "hbm", "achieved": round(gbs, 1),
                                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
                                 "algorithmic_bytes_per_launch": ab, "record_bytes_per_sample": rec_b}
-        if args.adaptive:
+        if rl is not None and args.adaptive:
             rl["adaptive_rounds"] = {"rounds": a_rounds, "samples_rendered": a_rendered,
                                      "samples_kept": int(my_samples),
                                      "speculation": round(a_rendered / max(my_samples, 1) - 1.0, 4)}
         cpu = None
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             log("cpu baseline")
             cpu = cpu_baseline(scene_data, {k: v for k, v in ropts.items() if k not in ("precision", "traversal")},
                                W, H, args.spp)
@@ -489,9 +534,7 @@ def main(argv=None):
             **({"frame_check": frame_check} if args.check else {}),
             "host_copy": "each timed step copies rank 0's u8 frame into pinned host memory (copy stream, "
                          "double-buffered: frame k's copy overlaps frame k+1's render; all inside the timed region)",
-            "parity": parity,
-            "roofline": rl,
-            "cpu_baseline": cpu,
+            **({"parity": parity, "roofline": rl, "cpu_baseline": cpu} if args.full else {}),
         }
         print(json.dumps(line), flush=True)
     rc = 0
@@ -552,20 +595,25 @@ def single_process_main(args) -> int:
     elapsed = sorted(reps)[len(reps) // 2]
     info = cam.multi_info()
     timed_rgb = host_frame.copy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_rgb)
     kernel_ms = max(info["path_ms"])
-    rad = np.zeros((H, W, 3), np.float32)
-    rgb = np.zeros((H, W, 3), np.uint8)
-    res = cam.render_region_multi(rgb, region, devices, radiance=rad)
-    parity = None if args.no_parity else parity_check(scene_data, ropts, args, timed_rgb, rgb, rad, res)
-    samples_per_step = int(res.samples["total"])
+    parity = rl = None
+    if args.full:
+        rad = np.zeros((H, W, 3), np.float32)
+        rgb = np.zeros((H, W, 3), np.uint8)
+        st = cam.render_region_multi(rgb, region, devices, radiance=rad)
+        parity = None if args.no_parity else parity_check(scene_data, ropts, args, timed_rgb, rgb, rad, st)
+    samples_per_step = int(st.samples["total"])  # the last timed step's; with --full the re-render's (equal)
     value = samples_per_step * args.steps / elapsed / 1e6
     n_dev = len(set(devices))
     key = f"{args.scene}_{W}x{H}_spp{args.spp}_d{args.depth}_{args.precision}_n1" + ("_adaptive" if args.adaptive else "")
-    # one device: the dominant kernel against VALU issue as in the per-rank path; several: the
-    # slowest device's path kernel (its share's counters are not collected separately)
-    rl = (roofline(key, rt.build_id(), samples_per_step, kernel_ms, None, W * H) if len(devices) == 1 else
-          {"bound": "valu", "kernel_ms": round(kernel_ms, 4), "frac": None,
-           "note": "slowest device's path kernel; per-device times in `multi`"})
+    if args.full:
+        # one device: the dominant kernel against VALU issue as in the per-rank path; several: the
+        # slowest device's path kernel (its share's counters are not collected separately)
+        rl = (roofline(key, rt.build_id(), samples_per_step, kernel_ms, None, W * H) if len(devices) == 1 else
+              {"bound": "valu", "kernel_ms": round(kernel_ms, 4), "frac": None,
+               "note": "slowest device's path kernel; per-device times in `multi`"})
     line = {
         "metric": metric_for(args.scene, W, H, args.spp, args.depth, args.adaptive), "value": round(value, 3),
         "unit": "Msamples/s", "n_gpus": n_dev, "steps": args.steps, "warmup": args.warmup,
@@ -586,9 +634,7 @@ def single_process_main(args) -> int:
                   "accum_ms": [round(x, 4) for x in info["accum_ms"]], "gather_ms": round(info["gather_ms"], 4),
                   "slab_tiles": info["slab_tiles"]},
         "host_copy": "each timed step is one rt_camera_render_multi call returning with the u8 frame in host memory",
-        "parity": parity,
-        "roofline": rl,
-        "cpu_baseline": None,
+        **({"parity": parity, "roofline": rl, "cpu_baseline": None} if args.full else {}),
     }
     print(json.dumps(line), flush=True)
     if parity is not None and not parity["ok"]:

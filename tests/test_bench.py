@@ -65,3 +65,37 @@ def test_bench_rejects_bad_repeat_counts():
             bench.parse_args(bad)
     a = bench.parse_args(["--single-process", "--gpus", "2", "--devices", "0,0"])
     assert a.single_process and a.devices == "0,0"
+
+
+def test_plain_run_times_the_steps_once_and_full_is_opt_in():
+    """A plain run times --steps steps once; --full restores the three repeats (median) and is
+    the switch for the counting launch, roofline, parity and CPU legs; --repeats still overrides."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (7, 2, 1, False, None)
+    assert bench.parse_args(["--full"]).repeats == 3 and bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--repeats", "5"]).repeats == 5
+    assert bench.parse_args(["--full", "--repeats", "2", "--dump-outputs", "x"]).dump_outputs == "x"
+
+
+def test_dump_outputs_writes_the_frame_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: frame.npy is the u8 frame, value for value, in float32; a frame above the
+    pixel cap is a seeded sample, the same pixels on every run, with their flat indices beside it."""
+    import numpy as np
+
+    import bench
+    g = np.random.default_rng(3)
+    frame = g.integers(0, 256, size=(21, 37, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), frame)
+    out = np.load(tmp_path / "a" / "frame.npy")
+    assert out.dtype == np.float32 and out.shape == (21, 37, 3) and np.array_equal(out, frame)
+    assert not (tmp_path / "a" / "frame_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_PIXELS", 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    px, idx = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "b" / "frame_index.npy")
+    assert px.dtype == np.float32 and px.shape == (100, 3) and idx.dtype == np.float64 and idx.shape == (100,)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 21 * 37
+    assert np.array_equal(px, frame.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_index.npy"))
+    assert np.array_equal(px, np.load(tmp_path / "c" / "frame.npy"))

@@ -1059,12 +1059,45 @@ def test_bench_two_ranks_one_gpu_assemble_the_frame(gpu):
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--no-cpu", "--no-count", "--check", "--width", "200", "--spp", "16"],
+                        "--warmup", "1", "--full", "--no-cpu", "--no-count", "--check", "--width", "200",
+                        "--spp", "16"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=str(root))
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     print({k: line[k] for k in ("value", "n_gpus", "ms_per_step", "frame_check")})
     assert line["n_gpus"] == 2 and line["frame_check"] is True
+
+
+def test_bench_plain_run_dumps_the_timed_frame(gpu, rt, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps once, prints the headline
+    keys without the --full legs, and --dump-outputs writes the last timed frame: float32,
+    equal to an in-process render of the same scene, options and seed."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--width", "72", "--spp", "8", "--depth", "8", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=120, env=env, cwd=str(root))
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["repeats"]["n"] == 1
+    assert line["ms_per_step"] > 0 and line["repeats"]["ms_per_step"] == [line["ms_per_step"]]
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    # value = samples per step / ms_per_step; ms_per_step is printed to 1 us, a step takes > 25 us
+    assert line["value"] == pytest.approx(72 * 72 * 8 / line["ms_per_step"] / 1e3, rel=2e-2)
+    assert not {"parity", "roofline", "cpu_baseline"} & set(line)
+    out = np.load(tmp_path / "frame.npy")
+    assert out.dtype == np.float32 and out.shape == (72, 72, 3)
+    cam = rt.create_camera_from_scene_data(rt.generate_scene_data({"type": "cornell"}),
+                                           {"width": 72, "samples": 8, "depth": 8, "aTolerance": 0, "seed": 0x5EED})
+    rgb = np.zeros((72, 72, 3), np.uint8)
+    cam.render(rgb)
+    assert np.array_equal(out, rgb)
 
 
 @pytest.mark.parametrize("groups,scene", [(3, "cornell"), (2, "spheres")])

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/pmc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 120 rocprofv3 -L > $R/gpurun_out/pmc/counters_list.txt 2>&1
-ARGS="${BENCH_ARGS:---steps 1 --warmup 0 --no-cpu}"
+ARGS="${BENCH_ARGS:---steps 1 --warmup 0 --full --no-cpu}"
 i=0
 while read -r line; do
   [ -z "$line" ] && continue

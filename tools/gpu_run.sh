@@ -27,7 +27,7 @@ TAG=$1; shift
 O=gpurun_out/$TAG
 mkdir -p $R/$O
 cd $R
-B="python bench.py --no-cpu"
+B="python bench.py --full --no-cpu"
 CFGS4=("" "--scene spheres --spp 64 --depth 8" "--scene rain --width 1920 --spp 512 --depth 16" \
        "--scene spheres100k --width 4096 --spp 16 --depth 100")
 CFG5="--scene spheres100k --width 4096 --spp 1024 --depth 100"
@@ -42,7 +42,7 @@ for step in "$@"; do
   case $step in
     pytest) run 900 pytest_gpu.log python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread -p no:cacheprovider || exit $? ;;
     pytest:*) run 900 pytest_k.log python -u -m pytest tests -m gpu -x -v -k "${step#pytest:}" --timeout 200 --timeout-method thread -p no:cacheprovider || exit $? ;;
-    bench) run 300 bench_default.log python bench.py || exit $? ;;
+    bench) run 300 bench_default.log python bench.py --full || exit $? ;;
     bench4)
       run 200 b_cornell.log $B --steps 5 --warmup 1 || exit $?
       run 200 b_spheres.log $B ${CFGS4[1]} --steps 5 --warmup 1 || exit $?
@@ -52,12 +52,12 @@ for step in "$@"; do
     adaptive) run 300 b_adaptive.log $B --adaptive --steps 3 --warmup 1 || exit $? ;;
     config5) run 600 b_config5.log $B $CFG5 --steps 1 --warmup 0 --no-count || exit $? ;;
     single)  # one process, all N GPUs through rt_camera_render_multi (device 0 repeated on a 1-GPU box)
-      run 300 b_single1.log python bench.py --single-process --gpus 1 --no-cpu --steps 10 || exit $?
-      run 300 b_single4.log python bench.py --single-process --gpus 4 --devices 0,0,0,0 --no-cpu --steps 10 || exit $? ;;
+      run 300 b_single1.log python bench.py --single-process --gpus 1 --full --no-cpu --steps 10 || exit $?
+      run 300 b_single4.log python bench.py --single-process --gpus 4 --devices 0,0,0,0 --full --no-cpu --steps 10 || exit $? ;;
     bench:*) a=${step#bench:}; run 300 b_extra_$(echo $a | tr -c 'a-z0-9' _ | cut -c1-40).log $B ${a//_/ } || exit $? ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o run \
-        --output-format csv -- python3 $R/bench.py --no-cpu > $R/$O/prof.log 2>&1) || exit $? ;;
+        --output-format csv -- python3 $R/bench.py --full --no-cpu > $R/$O/prof.log 2>&1) || exit $? ;;
     valu) VALU_DIR=$O/valu bash tools/pmc_valu.sh "${CFGS4[@]}" "--precision fp32" "--adaptive" || exit $? ;;
     valu5) VALU_DIR=$O/valu5 bash tools/pmc_valu.sh "$CFG5" || exit $? ;;
     traffic) TRAFFIC_DIR=$O/traffic bash tools/pmc_traffic.sh "${CFGS4[@]}" "--precision fp32" "--adaptive" || exit $? ;;
@@ -74,7 +74,7 @@ for step in "$@"; do
           [ -z "$arm" ] && continue
           if [ "$var" = "-" ]; then vv=""; else vv=$var; fi
           RT_AMD_VARIANT=$vv run ${TLIM:-200} ab/${tag}_${arm}.log python bench.py --steps ${STEPS:-5} --warmup 1 \
-            --no-cpu --no-count --no-parity $args || exit $?
+            --full --no-cpu --no-count --no-parity $args || exit $?
         done || exit $?
       done || exit $?
       python tools/ab_table.py $O/ab > $O/ab/table.txt ;;

@@ -12,7 +12,7 @@ for args in "$@"; do
   while read -r line; do
     [ -z "$line" ] && continue
     i=$((i+1))
-    timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $line -d $O/c${n}_p$i -o run --output-format csv -- python3 $R/bench.py $args --steps 2 --warmup 0 --no-cpu --no-count --no-parity > $O/c${n}_p$i.log 2>&1
+    timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $line -d $O/c${n}_p$i -o run --output-format csv -- python3 $R/bench.py $args --steps 2 --warmup 0 --full --no-cpu --no-count --no-parity > $O/c${n}_p$i.log 2>&1
     rc=$?; echo "cfg $n ($args) pass $i rc=$rc" >> $O/summary.txt
     [ $rc -ne 0 ] && exit $rc
   done < $R/tools/pmc_passes_lds.txt

@@ -11,7 +11,7 @@ n=0
 for args in "$@"; do
   n=$((n+1))
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d $R/$T/c${n}_$c -o run --output-format csv -- python3 $R/bench.py $args --steps 2 --warmup 0 --no-cpu --no-count --no-parity > $R/$T/c${n}_$c.log 2>&1
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d $R/$T/c${n}_$c -o run --output-format csv -- python3 $R/bench.py $args --steps 2 --warmup 0 --full --no-cpu --no-count --no-parity > $R/$T/c${n}_$c.log 2>&1
     rc=$?; echo "cfg $n ($args) $c rc=$rc" >> $R/$T/summary.txt
     [ $rc -ge 124 ] && exit $rc
   done
