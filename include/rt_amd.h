@@ -332,6 +332,80 @@ typedef struct {
 } rt_multi_info;
 int rt_camera_multi_info(rt_camera* cam, rt_multi_info* info);
 
+/* ---- Progressive rendering: resumable sample steps with a live preview ---------------------
+ * A session on a camera renders its region a few samples at a time. The path RNG is keyed by
+ * (pixel, sample) and PixelStats accumulates in sample order (src/render-utils/renderStats.ts:
+ * 76-88), so the frame a session reaches does not depend on how the steps were cut. A session
+ * is single-device (the calling thread's current device, as rt_camera_render_region) and owns
+ * its state and frame buffers: one-shot renders on the same camera between two steps neither
+ * disturb it nor are disturbed. No reference counterpart: the reference renders a frame in one
+ * call (src/camera.ts:388-431).
+ *
+ * A step renders the next min(n_samples, samples - samples_done) samples of every pixel still
+ * sampling and adds them to the pixel's running PixelStats in sample order, with the
+ * reference's convergence check (pixelConverged, src/camera.ts:348-368,406) after every sample;
+ * samples rendered past a pixel's convergence are dropped. A pixel is finished when it has
+ * converged or holds the camera's `samples`, and is never visited again; this holds for adaptive
+ * and fixed-spp cameras alike. The check after a step's last sample is made when the next step
+ * begins, so `active_pixels` counts the pixels that hold samples_done samples and have not
+ * reached the camera's `samples`.
+ *
+ * After every step the outputs describe ALL pixels of the region: finished pixels exactly as a
+ * one-shot render writes them, unfinished ones finalColor / writeColorToBuffer of their running
+ * PixelStats (the preview); stats is RenderStats.addPixel over all of them, each with the
+ * samples and bounces it has so far.
+ *
+ * Contract. With s = samples_done after a step, u8, radiance, px_samples, px_bounces and stats
+ * are bit-identical to rt_camera_render_region of a camera that differs only in `samples: s`,
+ * for mode default and bounces and s >= 2. (s = 1: a camera with samples > 1 jitters its first
+ * sample and a `samples: 1` camera does not, src/camera.ts:184. mode samples divides by the
+ * camera's own `samples`, src/camera.ts:333: its preview is min(n / samples, 1) of the session's
+ * camera.) When samples_done == samples the outputs equal the one-shot render of the same
+ * camera in every mode and both precisions.
+ *
+ * n_samples <= 0, a step / info / save without an open session and a region that is empty
+ * after clamping return RT_ERR_INVALID. A step on a finished session renders nothing and
+ * returns the final frame and stats again. Render errors (no background, emission stack)
+ * surface as in one-shot renders, from the samples that were kept only.
+ * rt_camera_release_device and rt_camera_destroy end the session. */
+typedef struct {
+    rt_region region;         /* the session's region, clamped to the image */
+    int32_t width, height;    /* the camera's image */
+    int32_t samples_done;     /* samples every unfinished pixel holds */
+    int32_t samples;          /* the camera's sample loop count (rt_camera_info.samples_loop) */
+    int32_t steps;            /* steps that rendered something */
+    int32_t done;             /* 1: no pixel is still sampling */
+    int32_t precision;        /* RT_PRECISION_* the session renders in */
+    uint32_t seed;
+    int64_t active_pixels;    /* pixels still sampling */
+    uint64_t state_bytes;     /* per-pixel state: the payload of a checkpoint blob */
+    char build_id[24];        /* rt_build_id of the library that holds / wrote the state */
+} rt_progressive_info;
+
+/* Opens a session over `region` (NULL: the whole image) at zero samples; an open one is dropped. */
+int rt_camera_progressive_begin(rt_camera* cam, const rt_region* region);
+/* One step (above). rgb / radiance: HOST buffers in full-frame layout as rt_camera_render_region,
+ * px_samples / px_bounces: HOST width*height int32; only the region is written; any may be NULL. */
+int rt_camera_progressive_step(rt_camera* cam, int32_t n_samples, uint8_t* rgb, float* radiance, int32_t* px_samples,
+                               int32_t* px_bounces, rt_render_stats* stats);
+int rt_camera_progressive_info(rt_camera* cam, rt_progressive_info* info);
+/* Checkpoint of the open session: a fixed header (magic, format version, rt_build_id, image size,
+ * region, precision, seed, samples, samples_done, steps, active pixels, a fingerprint of the
+ * flattened scene and the resolved camera options, payload length, checksums) and the per-pixel
+ * state (48 bytes per pixel slot: colour sum, n, finished flag, illuminance sums, bounce sum /
+ * min / max). The frame, the stats and the active list are rebuilt from the state, so the blob
+ * holds no frame. *blob is malloc'ed (rt_free). */
+int rt_camera_progressive_save(rt_camera* cam, uint8_t** blob, size_t* len);
+/* Opens a session from a blob (an open one is dropped on success). Refused with RT_ERR_INVALID
+ * and a message naming the first mismatch when the blob is truncated or corrupt, or when build
+ * id, image size, precision, seed, samples or the scene fingerprint differ from the camera's.
+ * The steps that follow give the frames the uninterrupted session would have given, bit for bit
+ * - in another camera object or another process. */
+int rt_camera_progressive_restore(rt_camera* cam, const uint8_t* blob, size_t len);
+/* Parses and validates a blob's header and checksums (host only, no device). */
+int rt_progressive_blob_info(const uint8_t* blob, size_t len, rt_progressive_info* info);
+int rt_camera_progressive_end(rt_camera* cam);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +28,7 @@
 #include "../../include/rt_amd.h"
 #include "json.hpp"
 #include "launch.hpp"
+#include "progressive.hpp"
 #include "scene.hpp"
 
 using namespace rt;
@@ -260,6 +262,7 @@ struct DevCtx {
         d_sbuf = nullptr;
         sbuf_cap = 0;
         free_adapt_buffers();
+        prog_free();
         if (d_acount) (void)hipFree(d_acount);
         d_acount = nullptr;
         if (h_acount) (void)hipHostFree(h_acount);
@@ -518,7 +521,8 @@ struct DevCtx {
 
     // Launch one render; returns after queueing (and synchronising if asked).
     void launch(const rt_region& region, int tile_group, int tile_groups, int prec, int trav, int count,
-                uint8_t* rgb, float* rad, int32_t* pxs, int32_t* pxb, int packed, hipStream_t stream) {
+                uint8_t* rgb, float* rad, int32_t* pxs, int32_t* pxb, int packed, hipStream_t stream,
+                int prog_len = 0) {  // > 0: one step of the progressive session (launch_progressive)
         const RtCamera& C = build.cam;
         if (tile_groups < 1 || tile_group < 0 || tile_group >= tile_groups)
             throw std::invalid_argument("tile_group must satisfy 0 <= tile_group < tile_groups");
@@ -614,7 +618,7 @@ struct DevCtx {
         // Instrumented launches (count == 1) keep the sequential kernel: a round renders samples
         // past a pixel's convergence, and the work counters would count them.
         const bool rounds = C.adaptive && count != 1 && env_flag("RT_AMD_ADAPT_ROUNDS", true);
-        if (C.n_samples <= 0 || !chunked || (C.adaptive && !rounds)) {
+        if (prog_len <= 0 && (C.n_samples <= 0 || !chunked || (C.adaptive && !rounds))) {
             // sequential-pixel kernel (pixelConverged needs each pixel's samples in one place)
             hip_check(hipEventRecord(pass_event(0, 0), stream), "hipEventRecord");
             hipError_t e = prec == PREC_FP32 ? launch_render_fp32(v, S, reg, out, g, nullptr, stream)
@@ -750,7 +754,9 @@ struct DevCtx {
             hip_check(e, "pt_chunk_kernel launch");
             hip_check(hipEventRecord(pass_event(pass, 1), stream), "hipEventRecord");
         };
-        if (rounds) {
+        if (prog_len > 0) {
+            launch_progressive(S, reg, out, g, sb, schedule, run_pass, pass, stream, prog_len);
+        } else if (rounds) {
             launch_adaptive_rounds(S, reg, out, g, mine, sb, schedule, run_pass, pass, stream);
         } else {
             // fixed spp: passes over at most sbuf_budget bytes of per-sample records
@@ -887,6 +893,139 @@ struct DevCtx {
             n += (long)std::min(kTile, reg.width - tx * kTile) * std::min(kTile, reg.height - ty * kTile);
         }
         return n;
+    }
+
+    // ---- Progressive session (rt_camera_progressive_*) ----------------------------------------
+    // State that outlives a call: every region pixel's running PixelStats under its slot (region
+    // tile * 64 + lane), the list of the slots still sampling, and the session's own frame. None
+    // of it is shared with one-shot renders (whose adaptive rounds use d_astate / d_act, and
+    // whose frame is d_rgb / d_rad); the record buffer, the stats words and the hand-out
+    // counter are per launch and shared.
+    struct ProgSession {
+        bool open = false;
+        rt_region region{};  // clamped to the image
+        int32_t precision = PREC_REF;
+        long slots = 0;      // region tiles * 64
+        int32_t done = 0;    // samples every unfinished pixel holds
+        int32_t steps = 0;
+        long n_act = 0;      // pixels still sampling
+        unsigned long long err = 0;             // error flags of the samples kept so far
+        unsigned long long words[ST_WORDS]{};   // RenderStats words of the current frame
+        ProgPix* d_state = nullptr;
+        int32_t* d_act = nullptr;
+        unsigned int* d_count = nullptr;
+        unsigned int* h_count = nullptr;
+        uint8_t* d_rgb = nullptr;
+        float* d_rad = nullptr;
+        int32_t* d_pxs = nullptr;
+        int32_t* d_pxb = nullptr;
+    } prog;
+
+    // (the caller has made `device` current, or this runs from release(), which has)
+    void prog_free() {
+        for (void* p : {(void*)prog.d_state, (void*)prog.d_act, (void*)prog.d_count, (void*)prog.d_rgb, (void*)prog.d_rad,
+                        (void*)prog.d_pxs, (void*)prog.d_pxb})
+            if (p) (void)hipFree(p);
+        if (prog.h_count) (void)hipHostFree(prog.h_count);
+        prog = ProgSession{};
+    }
+
+    // Opens a session over `region` (clamped; empty: invalid) with every pixel at zero samples.
+    void prog_alloc(const rt_region& region, int32_t precision) {
+        const RtCamera& C = build.cam;
+        const int x0 = std::max(region.x, 0), y0 = std::max(region.y, 0);
+        const int x1 = std::min(region.x + region.width, C.width), y1 = std::min(region.y + region.height, C.height);
+        if (x1 <= x0 || y1 <= y0) throw std::invalid_argument("progressive: the region is empty after clamping to the image");
+        prog_free();
+        ProgSession& P = prog;
+        P.region = rt_region{x0, y0, x1 - x0, y1 - y0};
+        P.precision = precision;
+        P.slots = (long)((P.region.width + kTile - 1) / kTile) * ((P.region.height + kTile - 1) / kTile) * kWave;
+        if (P.slots >= kItemCap) throw std::invalid_argument("progressive: the region has too many pixels");
+        const size_t px = (size_t)C.width * C.height;
+        try {
+            hip_check(hipMalloc(&P.d_state, (size_t)P.slots * sizeof(ProgPix)), "hipMalloc(progressive state)");
+            hip_check(hipMalloc(&P.d_act, (size_t)P.slots * sizeof(int32_t)), "hipMalloc(active list)");
+            hip_check(hipMalloc(&P.d_count, 2 * sizeof(unsigned int)), "hipMalloc");
+            hip_check(hipHostMalloc((void**)&P.h_count, 2 * sizeof(unsigned int), 0), "hipHostMalloc");
+            hip_check(hipMalloc(&P.d_rgb, px * 3), "hipMalloc(progressive frame)");
+            hip_check(hipMalloc(&P.d_rad, px * 3 * sizeof(float)), "hipMalloc(progressive frame)");
+            hip_check(hipMalloc(&P.d_pxs, px * sizeof(int32_t)), "hipMalloc(progressive frame)");
+            hip_check(hipMalloc(&P.d_pxb, px * sizeof(int32_t)), "hipMalloc(progressive frame)");
+            hip_check(hipMemset(P.d_state, 0, (size_t)P.slots * sizeof(ProgPix)), "hipMemset");
+        } catch (...) {
+            prog_free();
+            throw;
+        }
+        P.open = true;
+    }
+
+    RtRegion prog_reg() const { return RtRegion{prog.region.x, prog.region.y, prog.region.width, prog.region.height, 0, 1}; }
+    RenderOut prog_out() const { return RenderOut{prog.d_rgb, prog.d_rad, prog.d_pxs, prog.d_pxb, d_stats, d_counters, d_tile, 0}; }
+
+    // State -> the session's frame, RenderStats (added to d_stats: the caller has reset the
+    // words, launch() or launch_init_stats) and the active list; queued.
+    void prog_resolve(hipStream_t stream) {
+        ProgSession& P = prog;
+        hip_check(hipMemsetAsync(P.d_count, 0, 2 * sizeof(unsigned int), stream), "hipMemsetAsync");
+        const ProgResolve pr{P.d_state, (int32_t)P.slots, P.d_act, P.d_count};
+        const int tiles_x = std::max((P.region.width + kTile - 1) / kTile, 1);
+        hip_check(launch_resolve(dev_scene(), prog_reg(), prog_out(), tiles_x, pr, stream), "pt_resolve_kernel launch");
+    }
+
+    // Waits for the resolve pass: the frame's stats words (error flags: every kept sample's so
+    // far) and the number of pixels still sampling.
+    void prog_read(hipStream_t stream) {
+        ProgSession& P = prog;
+        unsigned long long wl[ST_WORDS * kStatStride];
+        hip_check(hipMemcpyAsync(wl, d_stats, sizeof wl, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
+        hip_check(hipMemcpyAsync(P.h_count, P.d_count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, stream),
+                  "hipMemcpyAsync");
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        for (int k = 0; k < ST_WORDS; ++k) P.words[k] = wl[k * kStatStride];
+        P.err |= P.words[ST_ERROR];
+        P.words[ST_ERROR] = P.err;
+        P.n_act = (long)P.h_count[0];
+    }
+
+    // A new or restored session's first resolve (no path kernel): frame, stats, active list.
+    void prog_start(hipStream_t stream) {
+        hip_check(launch_init_stats(d_stats, nullptr, d_tile, stream), "init_stats");
+        prog_resolve(stream);
+        prog_read(stream);
+    }
+
+    // One step of the session, from launch(): samples [done, done + len) of the active pixels on
+    // the chunked / pool kernel like an adaptive round (16-byte records, error flags in the
+    // records), in record passes under the record budget, each settled into the state
+    // (pt_settle_kernel); then one resolve pass over the whole region.
+    template <class Sched, class Pass>
+    void launch_progressive(DevScene& S, const RtRegion& reg, const RenderOut& out, const LaunchGeom& g, SampleBuf& sb,
+                            Sched& schedule, Pass& run_pass, int& pass, hipStream_t stream, int len) {
+        ProgSession& P = prog;
+        const long n_act = P.n_act;
+        sb.s_base = P.done;
+        sb.err_in_rec = 1;
+        sb.rec12 = 0;
+        sb.stride_slot = 1;
+        sb.tile0 = 0;
+        schedule((double)n_act, len);
+        const size_t rec_per_slot = (size_t)len * sizeof(float4);
+        // passes of whole 64-slot groups (items are numbered per group of 64 slots)
+        const long pass_slots =
+            kWave * pass_units((n_act + kWave - 1) / kWave, kWave, chunks_per_slot(sb), rec_per_slot * kWave, sbuf_budget());
+        ensure_sbuf((size_t)pass_slots * rec_per_slot);
+        sb.rec = d_sbuf;
+        const ProgPass pp{P.d_state, len};
+        for (long a0 = 0; a0 < n_act; a0 += pass_slots, ++pass) {
+            sb.slots = (int32_t)std::min<long>(pass_slots, n_act - a0);
+            sb.stride_s = sb.slots;
+            sb.act = P.d_act + a0;
+            run_pass(pass == 0);
+            hip_check(launch_settle(S, reg, out, g.tiles_x, sb, pp, stream), "pt_settle_kernel launch");
+            if (a0 + pass_slots >= n_act) prog_resolve(stream);  // (timed with the last pass's settle)
+            hip_check(hipEventRecord(pass_event(pass, 2), stream), "hipEventRecord");
+        }
     }
 
     int adapt_rounds = 0;                   // rounds of the last adaptive render
@@ -1069,6 +1208,13 @@ static Rccl& rccl() {
     return *lib;
 }
 
+// The current HIP device of the calling thread, restored when the scope ends.
+struct DeviceScope {
+    int prev = 0;
+    DeviceScope() { (void)hipGetDevice(&prev); }
+    ~DeviceScope() { (void)hipSetDevice(prev); }
+};
+
 struct rt_camera : CamHost {
     std::mutex mu;
     std::vector<std::unique_ptr<DevCtx>> ctxs;
@@ -1090,18 +1236,25 @@ struct rt_camera : CamHost {
         hip_check(hipGetDevice(&dev), "hipGetDevice");
         return ctx(dev, 0);
     }
+    DevCtx* prog = nullptr;  // the context that holds the open progressive session
     void release() {
         multi.clear();
         last = nullptr;
+        prog = nullptr;  // (the session's buffers go with its context)
         ctxs.clear();
     }
-};
-
-// The current HIP device of the calling thread, restored when the scope ends.
-struct DeviceScope {
-    int prev = 0;
-    DeviceScope() { (void)hipGetDevice(&prev); }
-    ~DeviceScope() { (void)hipSetDevice(prev); }
+    // the open session's context; a step, info or save without one is an argument error
+    DevCtx& session(const char* what) {
+        if (!prog || !prog->prog.open) throw std::invalid_argument(std::string(what) + ": no progressive session is open");
+        return *prog;
+    }
+    void end_session() {
+        if (!prog) return;
+        DeviceScope scope;
+        (void)hipSetDevice(prog->device);
+        prog->prog_free();
+        prog = nullptr;
+    }
 };
 
 // Single-process multi-GPU render (rt_camera_render_multi). Entry g of `devs` renders tile
@@ -1269,6 +1422,159 @@ static void png_out(DevCtx& c, hipStream_t stream, uint8_t** out, size_t* out_le
     std::memcpy(b, png.data(), png.size());
     *out = b;
     *out_len = png.size();
+}
+
+// ---- Progressive sessions: checkpoint blob --------------------------------------------------
+// [ProgBlobHeader][ProgPix x slots], little-endian as the host writes it. The header's checksum
+// covers the header up to that field, the payload's the state bytes (FNV-1a, 64 bit).
+static uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) {
+    const unsigned char* p = static_cast<const unsigned char*>(data);
+    for (size_t k = 0; k < n; ++k) h = (h ^ p[k]) * 1099511628211ull;
+    return h;
+}
+
+static const char kProgMagic[8] = {'R', 'T', 'P', 'R', 'O', 'G', 0x1a, '\n'};
+constexpr uint32_t kProgBlobVersion = 1;
+struct ProgBlobHeader {
+    char magic[8];
+    uint32_t version, header_bytes;
+    char build_id[24];
+    int32_t width, height;
+    int32_t rx, ry, rw, rh;
+    int32_t precision;
+    uint32_t seed;
+    double samples;        // RenderOptions.samples
+    int32_t samples_loop;  // its loop count
+    int32_t samples_done;
+    int32_t steps;
+    int32_t reserved;
+    int64_t active_pixels;
+    uint64_t err_flags;    // ERR_* of the samples kept so far
+    uint64_t fingerprint;  // flattened scene + resolved camera options
+    uint64_t payload_bytes, payload_checksum;
+    uint64_t header_checksum;
+};
+static_assert(sizeof(ProgBlobHeader) == 144 && offsetof(ProgBlobHeader, header_checksum) == 136, "blob header layout");
+
+// Fingerprint of what a session's samples depend on: the flattened scene (nodes, primitives,
+// materials, lights) and every resolved camera / render option, field by field (no padding).
+static uint64_t prog_fingerprint(const CamHost& h) {
+    const SceneBuild& b = h.build;
+    uint64_t f = fnv1a(b.nodes.data(), b.nodes.size() * sizeof(RtNode));
+    f = fnv1a(b.prims.data(), b.prims.size() * sizeof(RtPrim), f);
+    f = fnv1a(b.mats.data(), b.mats.size() * sizeof(RtMat), f);
+    f = fnv1a(b.lights.data(), b.lights.size() * sizeof(RtLight), f);
+    const RtCamera& C = b.cam;
+    auto add = [&](const auto& v) { f = fnv1a(&v, sizeof v, f); };
+    add(C.pixel00); add(C.du); add(C.dv); add(C.center); add(C.ddu); add(C.ddv); add(C.bg_top); add(C.bg_bottom);
+    add(C.aperture); add(C.samples); add(C.a_tolerance); add(C.a_batch); add(C.depth_raw);
+    add(C.width); add(C.height); add(C.n_samples); add(C.depth); add(C.roulette); add(C.roulette_depth);
+    add(C.mode); add(C.adaptive); add(C.n_lights); add(C.has_background); add(C.emissive_scatter);
+    add(C.n_nodes); add(C.n_prims); add(C.n_mats); add(C.seed);
+    return f;
+}
+
+// Validates a blob (length, magic, version, checksums) and returns its header; the state
+// follows at blob + sizeof(ProgBlobHeader).
+static ProgBlobHeader prog_parse_blob(const uint8_t* blob, size_t len) {
+    if (!blob || len == 0) throw std::invalid_argument("progressive blob: empty");
+    if (len < sizeof(ProgBlobHeader))
+        throw std::invalid_argument("progressive blob: truncated, " + std::to_string(len) + " bytes are less than the " +
+                                    std::to_string(sizeof(ProgBlobHeader)) + "-byte header");
+    ProgBlobHeader h;
+    std::memcpy(&h, blob, sizeof h);
+    if (std::memcmp(h.magic, kProgMagic, sizeof kProgMagic) != 0)
+        throw std::invalid_argument("progressive blob: bad magic (not a progressive checkpoint)");
+    if (h.version != kProgBlobVersion || h.header_bytes != sizeof(ProgBlobHeader))
+        throw std::invalid_argument("progressive blob: format version " + std::to_string(h.version) + " is not " +
+                                    std::to_string(kProgBlobVersion));
+    if (fnv1a(&h, offsetof(ProgBlobHeader, header_checksum)) != h.header_checksum)
+        throw std::invalid_argument("progressive blob: corrupt header (checksum mismatch)");
+    const long slots = h.rw > 0 && h.rh > 0 ? (long)((h.rw + kTile - 1) / kTile) * ((h.rh + kTile - 1) / kTile) * kWave : 0;
+    if (slots <= 0 || h.payload_bytes != (uint64_t)slots * sizeof(ProgPix))
+        throw std::invalid_argument("progressive blob: corrupt header (payload length does not fit the region)");
+    if (len < sizeof(ProgBlobHeader) + h.payload_bytes)
+        throw std::invalid_argument("progressive blob: truncated, " + std::to_string(len) + " of " +
+                                    std::to_string(sizeof(ProgBlobHeader) + h.payload_bytes) + " bytes");
+    if (len > sizeof(ProgBlobHeader) + h.payload_bytes)
+        throw std::invalid_argument("progressive blob: corrupt (bytes after the payload)");
+    if (fnv1a(blob + sizeof(ProgBlobHeader), (size_t)h.payload_bytes) != h.payload_checksum)
+        throw std::invalid_argument("progressive blob: corrupt payload (checksum mismatch)");
+    return h;
+}
+
+static void prog_info_from_header(const ProgBlobHeader& h, rt_progressive_info* info) {
+    *info = rt_progressive_info{};
+    info->region = rt_region{h.rx, h.ry, h.rw, h.rh};
+    info->width = h.width;
+    info->height = h.height;
+    info->samples_done = h.samples_done;
+    info->samples = h.samples_loop;
+    info->steps = h.steps;
+    info->done = h.active_pixels == 0 || h.samples_done >= h.samples_loop;
+    info->precision = h.precision;
+    info->seed = h.seed;
+    info->active_pixels = h.active_pixels;
+    info->state_bytes = h.payload_bytes;
+    std::memcpy(info->build_id, h.build_id, sizeof info->build_id);
+    info->build_id[sizeof info->build_id - 1] = 0;
+}
+
+// The open session's header (payload fields left to the caller).
+static ProgBlobHeader prog_header(const rt_camera* cam, const DevCtx& c) {
+    const DevCtx::ProgSession& P = c.prog;
+    const RtCamera& C = cam->build.cam;
+    ProgBlobHeader h{};
+    std::memcpy(h.magic, kProgMagic, sizeof kProgMagic);
+    h.version = kProgBlobVersion;
+    h.header_bytes = sizeof(ProgBlobHeader);
+    std::strncpy(h.build_id, RT_BUILD_ID, sizeof h.build_id - 1);
+    h.width = C.width;
+    h.height = C.height;
+    h.rx = P.region.x;
+    h.ry = P.region.y;
+    h.rw = P.region.width;
+    h.rh = P.region.height;
+    h.precision = P.precision;
+    h.seed = C.seed;
+    h.samples = C.samples;
+    h.samples_loop = C.n_samples;
+    h.samples_done = P.done;
+    h.steps = P.steps;
+    h.active_pixels = P.n_act;
+    h.err_flags = P.err;
+    h.fingerprint = prog_fingerprint(*cam);
+    h.payload_bytes = (uint64_t)P.slots * sizeof(ProgPix);
+    return h;
+}
+
+// Queues the copy of the session region's rows of a full-frame device array (`elem` bytes per
+// pixel) into the caller's host array of the same layout.
+static void prog_copy_out(const DevCtx& c, void* host, const void* dev, size_t elem, hipStream_t stream) {
+    if (!host) return;
+    const rt_region& r = c.prog.region;
+    const size_t pitch = (size_t)c.build.cam.width * elem;
+    const size_t off = ((size_t)r.y * c.build.cam.width + r.x) * elem;
+    hip_check(hipMemcpy2DAsync((char*)host + off, pitch, (const char*)dev + off, pitch, (size_t)r.width * elem, r.height,
+                               hipMemcpyDeviceToHost, stream),
+              "hipMemcpy2DAsync");
+}
+
+// Runs f under the camera's lock with the single-device entries' error mapping.
+template <class F>
+static int camera_call(rt_camera* cam, F&& f) {
+    if (!cam) return set_error(RT_ERR_INVALID, "null camera");
+    std::lock_guard<std::mutex> lock(cam->mu);
+    try {
+        f();
+        return RT_OK;
+    } catch (const HipError& e) {
+        return set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        return set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_RENDER, e.what());
+    }
 }
 
 extern "C" {
@@ -1718,6 +2024,148 @@ int rt_camera_multi_info(rt_camera* cam, rt_multi_info* info) {
         hip_check(hipEventSynchronize(root.ev_gather1), "hipEventSynchronize");
         hip_check(hipEventElapsedTime(&info->gather_ms, root.ev_gather0, root.ev_gather1), "hipEventElapsedTime");
     });
+}
+
+int rt_camera_progressive_begin(rt_camera* cam, const rt_region* region) {
+    return camera_call(cam, [&] {
+        const RtCamera& C = cam->build.cam;
+        const rt_region r = region ? *region : rt_region{0, 0, C.width, C.height};
+        // (checked before the device is touched; prog_alloc clamps the same way)
+        if (std::min(r.x + r.width, C.width) <= std::max(r.x, 0) || std::min(r.y + r.height, C.height) <= std::max(r.y, 0))
+            throw std::invalid_argument("rt_camera_progressive_begin: the region is empty after clamping to the image");
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        if (cam->prog && cam->prog != &c) cam->end_session();
+        c.prog_alloc(r, cam->precision);  // (throws before dropping an open session on a bad region)
+        cam->prog = &c;
+        try {
+            c.prog_start(nullptr);
+        } catch (...) {
+            cam->end_session();
+            throw;
+        }
+    });
+}
+
+int rt_camera_progressive_step(rt_camera* cam, int32_t n_samples, uint8_t* rgb, float* radiance, int32_t* px_samples,
+                               int32_t* px_bounces, rt_render_stats* stats) {
+    return camera_call(cam, [&] {
+        DevCtx& c = cam->session("rt_camera_progressive_step");
+        if (n_samples <= 0) throw std::invalid_argument("rt_camera_progressive_step: n_samples must be positive");
+        int dev = 0;
+        hip_check(hipGetDevice(&dev), "hipGetDevice");
+        if (dev != c.device) throw std::invalid_argument("rt_camera_progressive_step: the session lives on another device");
+        DevCtx::ProgSession& P = c.prog;
+        const RtCamera& C = cam->build.cam;
+        const hipStream_t stream = nullptr;
+        const int len = std::min<long>(n_samples, (long)C.n_samples - P.done);
+        if (len > 0 && P.n_act > 0) {  // (a finished session renders nothing)
+            cam->last = &c;
+            cam->multi.clear();
+            c.launch(P.region, 0, 1, P.precision, cam->traversal, 0, P.d_rgb, P.d_rad, P.d_pxs, P.d_pxb, 0, stream, len);
+            c.prog_read(stream);
+            P.done += len;
+            ++P.steps;
+        }
+        DevCtx::stats_from_words(P.words, stats);  // throws the render errors of the samples kept
+        prog_copy_out(c, rgb, P.d_rgb, 3, stream);
+        prog_copy_out(c, radiance, P.d_rad, 3 * sizeof(float), stream);
+        prog_copy_out(c, px_samples, P.d_pxs, sizeof(int32_t), stream);
+        prog_copy_out(c, px_bounces, P.d_pxb, sizeof(int32_t), stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_progressive_info(rt_camera* cam, rt_progressive_info* info) {
+    if (!info) return set_error(RT_ERR_INVALID, "null argument");
+    return camera_call(cam, [&] {
+        DevCtx& c = cam->session("rt_camera_progressive_info");
+        prog_info_from_header(prog_header(cam, c), info);
+    });
+}
+
+int rt_camera_progressive_save(rt_camera* cam, uint8_t** blob, size_t* len) {
+    if (!blob || !len) return set_error(RT_ERR_INVALID, "null argument");
+    return camera_call(cam, [&] {
+        DevCtx& c = cam->session("rt_camera_progressive_save");
+        ProgBlobHeader h = prog_header(cam, c);
+        const size_t total = sizeof h + (size_t)h.payload_bytes;
+        uint8_t* b = (uint8_t*)std::malloc(total);
+        if (!b) throw std::runtime_error("out of memory");
+        DeviceScope scope;
+        hipError_t e = hipSetDevice(c.device);
+        if (e == hipSuccess) e = hipMemcpy(b + sizeof h, c.prog.d_state, (size_t)h.payload_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            std::free(b);
+            hip_check(e, "hipMemcpy(progressive state)");
+        }
+        h.payload_checksum = fnv1a(b + sizeof h, (size_t)h.payload_bytes);
+        h.header_checksum = fnv1a(&h, offsetof(ProgBlobHeader, header_checksum));
+        std::memcpy(b, &h, sizeof h);
+        *blob = b;
+        *len = total;
+    });
+}
+
+int rt_camera_progressive_restore(rt_camera* cam, const uint8_t* blob, size_t len) {
+    return camera_call(cam, [&] {
+        const ProgBlobHeader h = prog_parse_blob(blob, len);
+        const RtCamera& C = cam->build.cam;
+        auto refuse = [](const std::string& what) {
+            throw std::invalid_argument("rt_camera_progressive_restore: the blob's " + what);
+        };
+        char bid[sizeof h.build_id] = {};
+        std::strncpy(bid, RT_BUILD_ID, sizeof bid - 1);
+        if (std::memcmp(bid, h.build_id, sizeof bid) != 0)
+            refuse("build id " + std::string(h.build_id, strnlen(h.build_id, sizeof h.build_id)) +
+                   " differs from this library's " + RT_BUILD_ID);
+        if (h.width != C.width || h.height != C.height)
+            refuse("image dimensions " + std::to_string(h.width) + "x" + std::to_string(h.height) +
+                   " differ from the camera's " + std::to_string(C.width) + "x" + std::to_string(C.height));
+        if (h.precision != cam->precision)
+            refuse(std::string("precision ") + (h.precision == PREC_FP32 ? "fp32" : "ref") + " differs from the camera's " +
+                   (cam->precision == PREC_FP32 ? "fp32" : "ref"));
+        if (h.seed != C.seed)
+            refuse("seed " + std::to_string(h.seed) + " differs from the camera's " + std::to_string(C.seed));
+        if (std::memcmp(&h.samples, &C.samples, sizeof(double)) != 0 || h.samples_loop != C.n_samples)
+            refuse("samples " + std::to_string(h.samples) + " differ from the camera's " + std::to_string(C.samples));
+        if (h.fingerprint != prog_fingerprint(*cam)) refuse("scene / render options fingerprint differs from the camera's");
+        if (h.samples_done < 0 || h.samples_done > h.samples_loop || h.rx < 0 || h.ry < 0 || h.rx + h.rw > C.width ||
+            h.ry + h.rh > C.height)
+            refuse("header is inconsistent (region or sample count out of range)");
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        if (cam->prog && cam->prog != &c) cam->end_session();
+        c.prog_alloc(rt_region{h.rx, h.ry, h.rw, h.rh}, h.precision);
+        cam->prog = &c;
+        try {
+            DevCtx::ProgSession& P = c.prog;
+            hip_check(hipMemcpy(P.d_state, blob + sizeof h, (size_t)h.payload_bytes, hipMemcpyHostToDevice),
+                      "hipMemcpy(progressive state)");
+            P.done = h.samples_done;
+            P.steps = h.steps;
+            P.err = h.err_flags;
+            c.prog_start(nullptr);
+            if (P.n_act != h.active_pixels) refuse("state does not match its header (active pixel count)");
+        } catch (...) {
+            cam->end_session();
+            throw;
+        }
+    });
+}
+
+int rt_progressive_blob_info(const uint8_t* blob, size_t len, rt_progressive_info* info) {
+    if (!info) return set_error(RT_ERR_INVALID, "null argument");
+    try {
+        prog_info_from_header(prog_parse_blob(blob, len), info);
+        return RT_OK;
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_INVALID, e.what());
+    }
+}
+
+int rt_camera_progressive_end(rt_camera* cam) {
+    return camera_call(cam, [&] { cam->end_session(); });
 }
 
 int rt_camera_release_device(rt_camera* cam) {

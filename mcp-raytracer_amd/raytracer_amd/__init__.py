@@ -8,15 +8,19 @@ This package is the host-side mirror of the reference's TypeScript surface:
     generate_scene_data / create_camera_from_scene_data / generate_scene  (src/scenes/scenes.ts)
     Camera.render_region / Camera.render -> RenderStats                  (src/camera.ts)
     generate_image_buffer                                                (src/raytracer.ts)
+
+plus progressive rendering, which the reference lacks: Camera.progressive / Camera.resume ->
+ProgressiveRender (resumable sample steps with a preview and checkpoints).
 """
-from ._lib import RtError, build_id, device_count
-from .camera import Camera, RenderStats, rng_stream
+from ._lib import RtError, build_id, device_count, progressive_blob_info
+from .camera import Camera, ProgressiveRender, RenderStats, rng_stream
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
                      generate_scene_data, generateScene, generateSceneData)
 
 __all__ = [
-    "Camera", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
+    "Camera", "ProgressiveRender", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
+    "progressive_blob_info",
     "generate_scene_data", "create_camera_from_scene_data", "generate_scene",
     "generate_image_buffer", "divide_into_regions",
     "generateSceneData", "createCameraFromSceneData", "generateScene", "generateImageBuffer",

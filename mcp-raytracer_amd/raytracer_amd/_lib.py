@@ -75,6 +75,21 @@ class RtMultiInfo(C.Structure):
                 ("gather_ms", C.c_float), ("plan", RtMultiPlan)]
 
 
+class RtProgressiveInfo(C.Structure):
+    _fields_ = [("region", RtRegion), ("width", C.c_int32), ("height", C.c_int32),
+                ("samples_done", C.c_int32), ("samples", C.c_int32), ("steps", C.c_int32), ("done", C.c_int32),
+                ("precision", C.c_int32), ("seed", C.c_uint32), ("active_pixels", C.c_int64),
+                ("state_bytes", C.c_uint64), ("build_id", C.c_char * 24)]
+
+    def as_dict(self) -> dict:
+        r = self.region
+        return {"region": (r.x, r.y, r.width, r.height), "width": self.width, "height": self.height,
+                "samples_done": self.samples_done, "samples": self.samples, "steps": self.steps,
+                "done": bool(self.done), "precision": "fp32" if self.precision == 1 else "ref", "seed": self.seed,
+                "active_pixels": self.active_pixels, "state_bytes": self.state_bytes,
+                "build_id": self.build_id.decode()}
+
+
 class RtError(RuntimeError):
     """An error returned through the C ABI (the reference would throw an Error)."""
 
@@ -131,6 +146,14 @@ _SIGS = {
     "rt_camera_render_png_multi": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(RtRenderStats),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "rt_camera_multi_info": (C.c_int, [C.c_void_p, C.POINTER(RtMultiInfo)]),
+    "rt_camera_progressive_begin": (C.c_int, [C.c_void_p, C.POINTER(RtRegion)]),
+    "rt_camera_progressive_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(RtRenderStats)]),
+    "rt_camera_progressive_info": (C.c_int, [C.c_void_p, C.POINTER(RtProgressiveInfo)]),
+    "rt_camera_progressive_save": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_camera_progressive_restore": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "rt_progressive_blob_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(RtProgressiveInfo)]),
+    "rt_camera_progressive_end": (C.c_int, [C.c_void_p]),
 }
 
 _lib = None
@@ -198,6 +221,16 @@ def multi_plan(region, width: int, height: int, n_devices: int) -> dict:
             "slab_tiles": p.slab_tiles, "tiles": p.tiles, "slab_bytes_rgb": p.slab_bytes_rgb,
             "slab_bytes_radiance": p.slab_bytes_radiance, "stats_offset": p.stats_offset,
             "group_tiles": list(p.group_tiles)[:p.n_devices]}
+
+
+def progressive_blob_info(blob: bytes) -> dict:
+    """rt_progressive_blob_info: a checkpoint blob's header, parsed and validated (length,
+    magic, version, checksums) on the host - region, samples_done, samples, steps, done,
+    active_pixels, precision, seed, state_bytes, build_id. Raises RtError on a bad blob."""
+    info = RtProgressiveInfo()
+    blob = bytes(blob)
+    check(load().rt_progressive_blob_info(blob, len(blob), C.byref(info)))
+    return info.as_dict()
 
 
 def device_count() -> int:

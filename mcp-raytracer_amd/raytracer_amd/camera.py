@@ -272,6 +272,23 @@ class Camera:
         _lib.check(self._lib.rt_camera_last_kernel(self._h, C.byref(n)))
         return self.KERNELS[int(n.value)]
 
+    # -- progressive rendering -------------------------------------------------
+    def progressive(self, region=None) -> "ProgressiveRender":
+        """Open a progressive session over `region` (default: the whole image) at zero
+        samples (rt_camera_progressive_begin). A camera holds one session: opening
+        another drops the first."""
+        reg = None if region is None else _region(region)
+        _lib.check(self._lib.rt_camera_progressive_begin(self._h, C.byref(reg) if reg is not None else None))
+        return ProgressiveRender(self)
+
+    def resume(self, blob: bytes) -> "ProgressiveRender":
+        """Open a session from ProgressiveRender.save()'s blob (rt_camera_progressive_restore).
+        Raises RtError naming the first mismatch when the blob is truncated or corrupt or was
+        saved by a camera with another scene, options, image size, precision or library build."""
+        blob = bytes(blob)
+        _lib.check(self._lib.rt_camera_progressive_restore(self._h, blob, len(blob)))
+        return ProgressiveRender(self)
+
     def release_device(self) -> None:
         """Free the device copies; the next render re-creates them (rt_camera_release_device)."""
         _lib.check(self._lib.rt_camera_release_device(self._h))
@@ -312,6 +329,87 @@ class Camera:
             self.close()
         except Exception:
             pass
+
+
+class ProgressiveRender:
+    """A progressive session of a Camera (rt_camera_progressive_*): the region rendered a few
+    samples at a time, every step returning the whole region's frame - finished pixels final,
+    the others previewed from the samples they have. The frame at samples_done == s is the
+    one-shot frame of the same camera with `samples: s`, bit for bit, however the steps were
+    cut. Use as a context manager, or close() it."""
+
+    def __init__(self, camera: Camera):
+        self._cam = camera
+
+    def _info(self) -> _lib.RtProgressiveInfo:
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        info = _lib.RtProgressiveInfo()
+        _lib.check(self._cam._lib.rt_camera_progressive_info(self._cam._h, C.byref(info)))
+        return info
+
+    def step(self, n: int, buffer=None, radiance=None, px_samples=None, px_bounces=None) -> RenderStats:
+        """Render the next `n` samples (clamped to the camera's `samples`) of every pixel still
+        sampling. `buffer` (u8 W*H*3), `radiance` (float32 W*H*3), `px_samples` / `px_bounces`
+        (int32 W*H) are optional caller-owned full-frame buffers; only the region is written.
+        Returns the RenderStats of the region's frame so far."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        cam = self._cam
+        px = cam.image_width * cam.image_height
+        ptr, _k0 = _host_ptr(buffer, cam.byte_length, "buffer")
+        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
+        sptr, _k2 = _host_ptr(px_samples, px * 4, "px_samples")
+        bptr, _k3 = _host_ptr(px_bounces, px * 4, "px_bounces")
+        st = _lib.RtRenderStats()
+        _lib.check(cam._lib.rt_camera_progressive_step(cam._h, int(n), ptr, rptr, sptr, bptr, C.byref(st)))
+        return RenderStats._from_c(st)
+
+    @property
+    def info(self) -> dict:
+        return self._info().as_dict()
+
+    @property
+    def samples_done(self) -> int:
+        return self._info().samples_done
+
+    @property
+    def samples(self) -> int:
+        return self._info().samples
+
+    @property
+    def active_pixels(self) -> int:
+        return self._info().active_pixels
+
+    @property
+    def steps(self) -> int:
+        return self._info().steps
+
+    @property
+    def done(self) -> bool:
+        return bool(self._info().done)
+
+    def save(self) -> bytes:
+        """The session's checkpoint blob (rt_camera_progressive_save); Camera.resume continues it."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        out, n = C.c_void_p(), C.c_size_t()
+        _lib.check(self._cam._lib.rt_camera_progressive_save(self._cam._h, C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            self._cam._lib.rt_free(out)
+
+    def close(self) -> None:
+        cam, self._cam = self._cam, None
+        if cam is not None and getattr(cam, "_h", None):
+            _lib.check(cam._lib.rt_camera_progressive_end(cam._h))
+
+    def __enter__(self) -> "ProgressiveRender":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
 
 
 def _dtypes():
