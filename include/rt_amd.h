@@ -406,6 +406,54 @@ int rt_camera_progressive_restore(rt_camera* cam, const uint8_t* blob, size_t le
 int rt_progressive_blob_info(const uint8_t* blob, size_t len, rt_progressive_info* info);
 int rt_camera_progressive_end(rt_camera* cam);
 
+/* ---- Guide buffers and the guided edge-avoiding a-trous filter -------------------------------
+ * No reference counterpart (the reference never filters a frame). Opt-in: no other call changes.
+ *
+ * Guides. One deterministic primary ray per pixel of the region: origin = the camera's centre,
+ * direction = pixel00 + du i + dv j - centre in fp32 - Camera.getRay of a `samples: 1`,
+ * `aperture: 0` camera (src/camera.ts:176-210): no jitter, no defocus sample (a camera with an
+ * aperture still gets this pinhole ray), no RNG. Always ref precision, the camera's own
+ * traversal, interval (0.001, inf). normal (float[3]: facing the ray), position (float[3]: the
+ * hit point), distance (float: sqrtf((dx dx + dy dy) + dz dz) of position - centre in fp32) and
+ * object (int32: index in SceneData.objects) equal the reference's world.hit of that ray bit
+ * for bit; a miss gives normal = position = 0, distance = 0, object = -1. glass and mirrors
+ * report their own surface, not what is seen through them.
+ *
+ * Filter. `levels` passes of a 5x5 B3-spline a-trous kernel at steps 1, 2, 4, ..., each tap
+ * weighted by max(0, n.n')^32, by the tap's distance from the centre pixel's tangent plane
+ * relative to sigma_plane * distance, and by the colour difference relative to sigma_color
+ * (halved per level); hit and miss pixels never mix, taps outside the region and non-finite
+ * taps are skipped, a non-finite pixel is copied through. Built from fp32 add, multiply, IEEE
+ * divide and square root in a fixed order: the result equals the NumPy restatement
+ * tests/denoise_ref.py (the normative definition) in every bit. rgb_out is the frame's own
+ * u8 of the filtered colour: floor(255.999 sqrt(c)) clamped to 0..255, non-positive / NaN -> 0.
+ *
+ * All buffers are HOST buffers in full-frame layout (normal / position / radiance width*height*3
+ * floats, distance / object width*height, rgb width*height*3 bytes); only the region (NULL: the
+ * whole image) is read and written; outputs may be NULL, and radiance_out may be radiance.
+ * Negative or non-finite parameters, levels > 8 and a region that is empty after clamping return
+ * RT_ERR_INVALID. rt_camera_release_device frees every device buffer of these calls. */
+typedef struct { int32_t levels; float sigma_color, sigma_plane; } rt_denoise_options;   /* NULL or a zero field = default (4, 0.5, 0.01) */
+int rt_camera_render_guides(rt_camera* cam, const rt_region* region, float* normal, float* position, float* distance,
+                            int32_t* object);
+/* explicit guides, no camera (the calling thread's current device) */
+int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,
+               const float* radiance, const float* normal, const float* position, const float* distance,
+               const int32_t* object, float* radiance_out, uint8_t* rgb_out);
+/* guides computed on the device (they never reach the host) */
+int rt_camera_denoise(rt_camera* cam, const rt_region* region, const rt_denoise_options* options, const float* radiance,
+                      float* radiance_out, uint8_t* rgb_out);
+/* The open progressive session's device frame as it stands after the last step, filtered over
+ * the session's region: nothing is uploaded. The region's guides are computed on first use and
+ * kept until the session ends. The session's state, frame and stats are not touched, so its
+ * later steps are those of a session that never called this. RT_ERR_INVALID without an open
+ * session and for a camera in mode bounces / samples (those frames are not radiance). */
+int rt_camera_progressive_denoise(rt_camera* cam, const rt_denoise_options* options, uint8_t* rgb, float* radiance);
+/* Device time of the camera's last rt_camera_denoise / rt_camera_progressive_denoise from HIP
+ * events: the guide pass (0 when a session reused its guides), each level (level_ms: 8 floats)
+ * and the whole span guide pass .. filtered frame (host copies excluded). Waits for the events. */
+int rt_camera_denoise_times(rt_camera* cam, int32_t* levels, float* guide_ms, float* level_ms, float* total_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/rt_amd.h"
+#include "denoise.hpp"
 #include "json.hpp"
 #include "launch.hpp"
 #include "progressive.hpp"
@@ -133,6 +134,114 @@ static std::vector<RtOnb> planar_onbs(const std::vector<RtPrim>& prims, int32_t*
     }
     *n_onb = n;
     return t;
+}
+
+// Region-packed device buffers of one filter call (denoise.hpp), grown on demand: the colour
+// ping-pong pair, the per-call guide plane, a guide pair, and the staging arrays the host
+// copies go through (radiance / normal / position float[3], distance, object, u8).
+struct DnBufs {
+    float4 *c0 = nullptr, *c1 = nullptr, *fn = nullptr, *gn = nullptr, *gp = nullptr;
+    float* stage = nullptr;  // 10 floats per pixel
+    int32_t* obj = nullptr;
+    uint8_t* u8 = nullptr;
+    size_t cap = 0;  // pixels
+    float* rad() const { return stage; }
+    float* nrm() const { return stage + 3 * cap; }
+    float* pos() const { return stage + 6 * cap; }
+    float* dist() const { return stage + 9 * cap; }
+    // (the caller has made the buffers' device current)
+    void free() {
+        for (void* p : {(void*)c0, (void*)c1, (void*)fn, (void*)gn, (void*)gp, (void*)stage, (void*)obj, (void*)u8})
+            if (p) (void)hipFree(p);
+        *this = DnBufs{};
+    }
+    void ensure(size_t n) {
+        if (n <= cap) return;
+        free();
+        try {
+            for (float4** p : {&c0, &c1, &fn, &gn, &gp}) hip_check(hipMalloc(p, n * sizeof(float4)), "hipMalloc(denoise)");
+            hip_check(hipMalloc(&stage, n * 10 * sizeof(float)), "hipMalloc(denoise)");
+            hip_check(hipMalloc(&obj, n * sizeof(int32_t)), "hipMalloc(denoise)");
+            hip_check(hipMalloc(&u8, n * 3), "hipMalloc(denoise)");
+        } catch (...) {
+            free();
+            throw;
+        }
+        cap = n;
+    }
+};
+
+// rt_denoise_options resolved: NULL or a zero field = the default.
+struct DnOpts {
+    int32_t levels = 4;
+    float sigma_color = 0.5f, sigma_plane = 0.01f;
+};
+static DnOpts dn_options(const rt_denoise_options* o, const std::string& who) {
+    DnOpts r;
+    if (!o) return r;
+    if (o->levels < 0 || o->levels > kDenoiseMaxLevels)
+        throw std::invalid_argument(who + ": levels must be 1.." + std::to_string(kDenoiseMaxLevels) + " (0: the default)");
+    if (!(o->sigma_color >= 0.0f) || !std::isfinite(o->sigma_color))
+        throw std::invalid_argument(who + ": sigma_color must be positive and finite (0: the default)");
+    if (!(o->sigma_plane >= 0.0f) || !std::isfinite(o->sigma_plane))
+        throw std::invalid_argument(who + ": sigma_plane must be positive and finite (0: the default)");
+    if (o->levels) r.levels = o->levels;
+    if (o->sigma_color != 0.0f) r.sigma_color = o->sigma_color;
+    if (o->sigma_plane != 0.0f) r.sigma_plane = o->sigma_plane;
+    return r;
+}
+
+// `region` (NULL: the whole image) clamped to a width x height image; empty: an argument error.
+constexpr long kDenoiseMaxPixels = 1l << 28;
+static rt_region dn_region(const rt_region* region, int32_t width, int32_t height, const std::string& who) {
+    const rt_region r = region ? *region : rt_region{0, 0, width, height};
+    const long x0 = std::max(r.x, 0), y0 = std::max(r.y, 0);
+    const long x1 = std::min<long>((long)r.x + r.width, width), y1 = std::min<long>((long)r.y + r.height, height);
+    if (x1 <= x0 || y1 <= y0) throw std::invalid_argument(who + ": the region is empty after clamping to the image");
+    if ((x1 - x0) * (y1 - y0) > kDenoiseMaxPixels) throw std::invalid_argument(who + ": the region has too many pixels");
+    return rt_region{(int32_t)x0, (int32_t)y0, (int32_t)(x1 - x0), (int32_t)(y1 - y0)};
+}
+
+// Queued copies between a host array in full-frame layout (`elem` bytes per pixel, image
+// width `width`) and a region-packed device array: the region's rows only.
+static void dn_upload(void* dev, const void* host, size_t elem, int32_t width, const rt_region& r, hipStream_t stream) {
+    const size_t off = ((size_t)r.y * width + r.x) * elem;
+    hip_check(hipMemcpy2DAsync(dev, (size_t)r.width * elem, (const char*)host + off, (size_t)width * elem,
+                               (size_t)r.width * elem, r.height, hipMemcpyHostToDevice, stream),
+              "hipMemcpy2DAsync");
+}
+static void dn_download(void* host, const void* dev, size_t elem, int32_t width, const rt_region& r, hipStream_t stream) {
+    if (!host) return;
+    const size_t off = ((size_t)r.y * width + r.x) * elem;
+    hip_check(hipMemcpy2DAsync((char*)host + off, (size_t)width * elem, dev, (size_t)r.width * elem,
+                               (size_t)r.width * elem, r.height, hipMemcpyDeviceToHost, stream),
+              "hipMemcpy2DAsync");
+}
+
+// The filter over a w x h region whose guides are gn / gp: colour and fn from `rad` (row pitch
+// `pitch_px` pixels, region at (x0, y0)), one launch per level over the ping-pong pair, then
+// the result into b.rad() / b.u8 (region-packed). ev (or null): levels + 3 events, recorded
+// before the pack pass, after it, after every level and after the unpack pass. Queued.
+static void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0,
+                      int w, int h, const DnOpts& o, bool want_rad, bool want_u8, hipStream_t stream, hipEvent_t* ev) {
+    int e = 0;
+    auto mark = [&] {
+        if (ev) hip_check(hipEventRecord(ev[e++], stream), "hipEventRecord");
+    };
+    mark();
+    hip_check(launch_denoise_pack(rad, pitch_px, x0, y0, w, h, gn, o.sigma_plane, b.c0, b.fn, stream), "denoise_pack_kernel");
+    mark();
+    float4 *src = b.c0, *dst = b.c1;
+    for (int lv = 0; lv < o.levels; ++lv) {
+        // 4^level / sigma_color^2: in double on the host, rounded to fp32 once
+        const float k_c = (float)(std::ldexp(1.0, 2 * lv) / ((double)o.sigma_color * (double)o.sigma_color));
+        hip_check(launch_denoise_level(src, dst, b.fn, gp, w, h, 1 << lv, k_c, stream), "denoise kernel");
+        mark();
+        std::swap(src, dst);
+    }
+    hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8 : nullptr, stream),
+              "denoise_unpack_kernel");
+    mark();
 }
 
 // The host half of a camera: the reference's Camera after createCameraFromSceneData
@@ -263,6 +372,13 @@ struct DevCtx {
         sbuf_cap = 0;
         free_adapt_buffers();
         prog_free();
+        dn.free();
+        if (d_prim_object) (void)hipFree(d_prim_object);
+        d_prim_object = nullptr;
+        for (hipEvent_t& e : dn_ev)
+            if (e) (void)hipEventDestroy(e), e = nullptr;
+        dn_ev.clear();
+        dn_levels = 0;
         if (d_acount) (void)hipFree(d_acount);
         d_acount = nullptr;
         if (h_acount) (void)hipHostFree(h_acount);
@@ -919,12 +1035,14 @@ struct DevCtx {
         float* d_rad = nullptr;
         int32_t* d_pxs = nullptr;
         int32_t* d_pxb = nullptr;
+        float4* d_gn = nullptr;  // the region's guides (denoise.hpp), computed by the first
+        float4* d_gp = nullptr;  // rt_camera_progressive_denoise of the session
     } prog;
 
     // (the caller has made `device` current, or this runs from release(), which has)
     void prog_free() {
         for (void* p : {(void*)prog.d_state, (void*)prog.d_act, (void*)prog.d_count, (void*)prog.d_rgb, (void*)prog.d_rad,
-                        (void*)prog.d_pxs, (void*)prog.d_pxb})
+                        (void*)prog.d_pxs, (void*)prog.d_pxb, (void*)prog.d_gn, (void*)prog.d_gp})
             if (p) (void)hipFree(p);
         if (prog.h_count) (void)hipHostFree(prog.h_count);
         prog = ProgSession{};
@@ -1026,6 +1144,41 @@ struct DevCtx {
             if (a0 + pass_slots >= n_act) prog_resolve(stream);  // (timed with the last pass's settle)
             hip_check(hipEventRecord(pass_event(pass, 2), stream), "hipEventRecord");
         }
+    }
+
+    // ---- Guides and the a-trous filter (denoise.hpp) -------------------------------------------
+    DnBufs dn;                         // one call's buffers (kept between calls)
+    int32_t* d_prim_object = nullptr;  // prim slot -> SceneData.objects index
+    // HIP events of the last filter call: [0, 1) the guide pass, then dn_filter's levels + 3
+    std::vector<hipEvent_t> dn_ev;
+    int dn_levels = 0;        // levels of the last call (0: none yet)
+    bool dn_guides = false;   // the last call ran the guide pass (a session computes it once)
+    hipEvent_t* dn_events(int levels) {
+        while ((int)dn_ev.size() < kDenoiseMaxLevels + 5) {
+            hipEvent_t e = nullptr;
+            hip_check(hipEventCreate(&e), "hipEventCreate");
+            dn_ev.push_back(e);
+        }
+        dn_levels = levels;
+        return dn_ev.data();
+    }
+
+    // The guide pass over `r` (clamped) into g, through the strategy `trav` resolves to; queued.
+    void launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream) {
+        const RtCamera& C = build.cam;
+        if (!d_prim_object) {
+            std::vector<int32_t> po(std::max<size_t>(C.n_prims, 1), -1);
+            std::copy(build.prim_object.begin(), build.prim_object.begin() + std::min(build.prim_object.size(), po.size()),
+                      po.begin());
+            hip_check(hipMalloc(&d_prim_object, po.size() * sizeof(int32_t)), "hipMalloc(prim_object)");
+            hip_check(hipMemcpy(d_prim_object, po.data(), po.size() * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        const int tr = effective_traversal(trav);
+        if (stack_lds_bytes(C.stack_depth, tr, C.n_prims) > (size_t)lds_max)
+            throw std::runtime_error("traversal stack exceeds the workgroup LDS (BVH too deep)");
+        hip_check(launch_guides(dev_scene(), tr, RtRegion{r.x, r.y, r.width, r.height, 0, 1}, d_prim_object, g, lds_max,
+                                stream),
+                  "guide_kernel launch");
     }
 
     int adapt_rounds = 0;                   // rounds of the last adaptive render
@@ -2166,6 +2319,155 @@ int rt_progressive_blob_info(const uint8_t* blob, size_t len, rt_progressive_inf
 
 int rt_camera_progressive_end(rt_camera* cam) {
     return camera_call(cam, [&] { cam->end_session(); });
+}
+
+// ---- Guides and the a-trous filter ------------------------------------------------------------
+int rt_camera_render_guides(rt_camera* cam, const rt_region* region, float* normal, float* position, float* distance,
+                            int32_t* object) {
+    return camera_call(cam, [&] {
+        const RtCamera& C = cam->build.cam;
+        const rt_region r = dn_region(region, C.width, C.height, "rt_camera_render_guides");
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        const hipStream_t stream = nullptr;
+        const int n = r.width * r.height;
+        DnBufs& b = c.dn;
+        b.ensure((size_t)n);
+        const DenoiseGuides g{b.gn, b.gp};
+        c.launch_guide_pass(r, cam->traversal, g, stream);
+        hip_check(launch_guides_unpack(g, n, b.nrm(), b.pos(), b.dist(), b.obj, stream), "guides_unpack_kernel");
+        dn_download(normal, b.nrm(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(position, b.pos(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(distance, b.dist(), sizeof(float), C.width, r, stream);
+        dn_download(object, b.obj, sizeof(int32_t), C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,
+               const float* radiance, const float* normal, const float* position, const float* distance,
+               const int32_t* object, float* radiance_out, uint8_t* rgb_out) {
+    DnBufs b;
+    int rc = RT_OK;
+    try {
+        if (width <= 0 || height <= 0) throw std::invalid_argument("rt_denoise: width and height must be positive");
+        if (!radiance || !normal || !position || !distance || !object)
+            throw std::invalid_argument("rt_denoise: radiance, normal, position, distance and object are required");
+        const DnOpts o = dn_options(options, "rt_denoise");
+        const rt_region r = dn_region(region, width, height, "rt_denoise");
+        const hipStream_t stream = nullptr;
+        const int n = r.width * r.height;
+        b.ensure((size_t)n);
+        dn_upload(b.rad(), radiance, 3 * sizeof(float), width, r, stream);
+        dn_upload(b.nrm(), normal, 3 * sizeof(float), width, r, stream);
+        dn_upload(b.pos(), position, 3 * sizeof(float), width, r, stream);
+        dn_upload(b.dist(), distance, sizeof(float), width, r, stream);
+        dn_upload(b.obj, object, sizeof(int32_t), width, r, stream);
+        const DenoiseGuides g{b.gn, b.gp};
+        hip_check(launch_guides_pack(g, n, b.nrm(), b.pos(), b.dist(), b.obj, stream), "guides_pack_kernel");
+        dn_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
+                  rgb_out != nullptr, stream, nullptr);
+        dn_download(radiance_out, b.rad(), 3 * sizeof(float), width, r, stream);
+        dn_download(rgb_out, b.u8, 3, width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    } catch (const HipError& e) {
+        rc = set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        rc = set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        rc = set_error(RT_ERR_RENDER, e.what());
+    }
+    b.free();
+    return rc;
+}
+
+int rt_camera_denoise(rt_camera* cam, const rt_region* region, const rt_denoise_options* options, const float* radiance,
+                      float* radiance_out, uint8_t* rgb_out) {
+    return camera_call(cam, [&] {
+        const RtCamera& C = cam->build.cam;
+        if (!radiance) throw std::invalid_argument("rt_camera_denoise: radiance is required");
+        const DnOpts o = dn_options(options, "rt_camera_denoise");
+        const rt_region r = dn_region(region, C.width, C.height, "rt_camera_denoise");
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        const hipStream_t stream = nullptr;
+        DnBufs& b = c.dn;
+        b.ensure((size_t)r.width * r.height);
+        hipEvent_t* ev = c.dn_events(o.levels);
+        dn_upload(b.rad(), radiance, 3 * sizeof(float), C.width, r, stream);
+        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+        c.launch_guide_pass(r, cam->traversal, DenoiseGuides{b.gn, b.gp}, stream);
+        c.dn_guides = true;
+        dn_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
+                  rgb_out != nullptr, stream, ev + 1);
+        dn_download(radiance_out, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(rgb_out, b.u8, 3, C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_progressive_denoise(rt_camera* cam, const rt_denoise_options* options, uint8_t* rgb, float* radiance) {
+    return camera_call(cam, [&] {
+        DevCtx& c = cam->session("rt_camera_progressive_denoise");
+        const RtCamera& C = cam->build.cam;
+        if (C.mode != MODE_DEFAULT)
+            throw std::invalid_argument("rt_camera_progressive_denoise: the frames of mode bounces / samples are not radiance");
+        const DnOpts o = dn_options(options, "rt_camera_progressive_denoise");
+        int dev = 0;
+        hip_check(hipGetDevice(&dev), "hipGetDevice");
+        if (dev != c.device)
+            throw std::invalid_argument("rt_camera_progressive_denoise: the session lives on another device");
+        DevCtx::ProgSession& P = c.prog;
+        const rt_region r = P.region;
+        const hipStream_t stream = nullptr;
+        const size_t n = (size_t)r.width * r.height;
+        DnBufs& b = c.dn;
+        b.ensure(n);
+        hipEvent_t* ev = c.dn_events(o.levels);
+        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+        c.dn_guides = !P.d_gn;
+        if (!P.d_gn) {  // the region's guides: computed once, freed with the session
+            try {
+                hip_check(hipMalloc(&P.d_gn, n * sizeof(float4)), "hipMalloc(session guides)");
+                hip_check(hipMalloc(&P.d_gp, n * sizeof(float4)), "hipMalloc(session guides)");
+                c.launch_guide_pass(r, cam->traversal, DenoiseGuides{P.d_gn, P.d_gp}, stream);
+            } catch (...) {
+                if (P.d_gn) (void)hipFree(P.d_gn);
+                if (P.d_gp) (void)hipFree(P.d_gp);
+                P.d_gn = P.d_gp = nullptr;
+                throw;
+            }
+        }
+        // the session's device frame as it stands after the last step: nothing is uploaded
+        dn_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, r.x, r.y, r.width, r.height, o, radiance != nullptr, rgb != nullptr,
+                  stream, ev + 1);
+        dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(rgb, b.u8, 3, C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_denoise_times(rt_camera* cam, int32_t* levels, float* guide_ms, float* level_ms, float* total_ms) {
+    if (!levels || !guide_ms || !level_ms || !total_ms) return set_error(RT_ERR_INVALID, "null argument");
+    return camera_call(cam, [&] {
+        DevCtx* c = nullptr;
+        for (auto& x : cam->ctxs)
+            if (x->dn_levels > 0) c = x.get();
+        if (!c) throw std::invalid_argument("rt_camera_denoise_times: no filter call yet");
+        DeviceScope scope;
+        hip_check(hipSetDevice(c->device), "hipSetDevice");
+        const int L = c->dn_levels;
+        hipEvent_t* ev = c->dn_ev.data();  // guide [0, 1), pack [1, 2), level l [2 + l, 3 + l), unpack
+        hip_check(hipEventSynchronize(ev[L + 3]), "hipEventSynchronize");
+        *levels = L;
+        *guide_ms = 0.0f;
+        if (c->dn_guides) hip_check(hipEventElapsedTime(guide_ms, ev[0], ev[1]), "hipEventElapsedTime");
+        for (int l = 0; l < kDenoiseMaxLevels; ++l) {
+            level_ms[l] = 0.0f;
+            if (l < L) hip_check(hipEventElapsedTime(&level_ms[l], ev[2 + l], ev[3 + l]), "hipEventElapsedTime");
+        }
+        hip_check(hipEventElapsedTime(total_ms, ev[0], ev[L + 3]), "hipEventElapsedTime");
+    });
 }
 
 int rt_camera_release_device(rt_camera* cam) {

@@ -10,17 +10,19 @@ This package is the host-side mirror of the reference's TypeScript surface:
     generate_image_buffer                                                (src/raytracer.ts)
 
 plus progressive rendering, which the reference lacks: Camera.progressive / Camera.resume ->
-ProgressiveRender (resumable sample steps with a preview and checkpoints).
+ProgressiveRender (resumable sample steps with a preview and checkpoints), and first-hit
+guide buffers with a guided edge-avoiding a-trous filter for low-sample frames:
+Camera.render_guides / Camera.denoise / denoise / ProgressiveRender.denoised.
 """
 from ._lib import RtError, build_id, device_count, progressive_blob_info
-from .camera import Camera, ProgressiveRender, RenderStats, rng_stream
+from .camera import Camera, ProgressiveRender, RenderStats, denoise, rng_stream
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
                      generate_scene_data, generateScene, generateSceneData)
 
 __all__ = [
     "Camera", "ProgressiveRender", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
-    "progressive_blob_info",
+    "progressive_blob_info", "denoise",
     "generate_scene_data", "create_camera_from_scene_data", "generate_scene",
     "generate_image_buffer", "divide_into_regions",
     "generateSceneData", "createCameraFromSceneData", "generateScene", "generateImageBuffer",

@@ -47,13 +47,17 @@ _UNITS = [
     ("pt_ref.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     ("pt_fp32.hip", ["-ffp-contract=fast", *_KERNEL_FLAGS], True),
     ("progressive.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # guide pass + a-trous filter: every fp32 operation must round once (no contraction; plain /
+    # and sqrtf are IEEE under hipcc's defaults) - the output equals tests/denoise_ref.py in every bit
+    ("denoise.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     ("frame.hip", [], True),
     ("png.hip", [], True),
     ("rt_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("scene.cpp", ["-ffp-contract=off"], False),
     ("image.cpp", [], False),
 ]
-_HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "png_deflate.hpp"]
+_HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
+            "png_deflate.hpp"]
 _LIBS = ["-lz"]
 
 

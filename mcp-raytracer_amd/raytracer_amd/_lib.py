@@ -90,6 +90,13 @@ class RtProgressiveInfo(C.Structure):
                 "build_id": self.build_id.decode()}
 
 
+class RtDenoiseOptions(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_plane", C.c_float)]
+
+
+DENOISE_MAX_LEVELS = 8
+
+
 class RtError(RuntimeError):
     """An error returned through the C ABI (the reference would throw an Error)."""
 
@@ -154,6 +161,15 @@ _SIGS = {
     "rt_camera_progressive_restore": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "rt_progressive_blob_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(RtProgressiveInfo)]),
     "rt_camera_progressive_end": (C.c_int, [C.c_void_p]),
+    "rt_camera_render_guides": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "rt_denoise": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.POINTER(RtDenoiseOptions), C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.POINTER(RtDenoiseOptions), C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "rt_camera_progressive_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseOptions), C.c_void_p, C.c_void_p]),
+    "rt_camera_denoise_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -83,6 +83,61 @@ def _host_ptr(buf, nbytes: int, what: str):
     return C.cast(cbuf, C.c_void_p), cbuf
 
 
+def _denoise_options(levels, sigma_color, sigma_plane) -> _lib.RtDenoiseOptions:
+    """rt_denoise_options (a zero field = the default; the library validates the rest)."""
+    return _lib.RtDenoiseOptions(int(levels), float(sigma_color), float(sigma_plane))
+
+
+def _f32_frame(a, shape, what: str):
+    """`a` as a C-contiguous float32 / int32 array of `shape` (no copy when it already is)."""
+    import numpy as np
+    dtype = np.int32 if what == "object" else np.float32
+    arr = np.ascontiguousarray(a, dtype=dtype)
+    if arr.size != int(np.prod(shape)):
+        raise ValueError(f"{what} must hold {'x'.join(str(v) for v in shape)} values, not {arr.size}")
+    return arr.reshape(shape)
+
+
+def _denoise_out(src, out):
+    """The array a filter call writes: `out` (which may be the input itself) or a copy of the
+    input, so the pixels outside the region come back unchanged."""
+    import numpy as np
+    if out is None:
+        return np.array(src, dtype=np.float32, copy=True)
+    if (not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]
+            or not out.flags["WRITEABLE"] or out.size != src.size):
+        raise ValueError("out must be a writable C-contiguous float32 array of the radiance's size")
+    return out
+
+
+def denoise(radiance, normal, position, distance, object, region=None, *, levels=4, sigma_color=0.5,
+            sigma_plane=0.01, rgb=None, out=None):
+    """rt_denoise: the guided edge-avoiding a-trous filter of a frame with explicit guides (as
+    Camera.render_guides returns them), no camera. radiance / normal / position: float32
+    (H, W, 3); distance float32, object int32: (H, W). Returns the filtered radiance (H, W, 3) -
+    a new array, or `out` (which may be `radiance` itself); only the region is filtered. `rgb`
+    (optional caller-owned u8 H*W*3) receives the region's u8. Equals tests/denoise_ref.py in
+    every bit."""
+    import numpy as np
+    rad = np.asarray(radiance)
+    if rad.ndim != 3 or rad.shape[2] != 3:
+        raise ValueError("radiance must have shape (H, W, 3)")
+    H, W = rad.shape[:2]
+    rad = _f32_frame(rad, (H, W, 3), "radiance")
+    nrm = _f32_frame(normal, (H, W, 3), "normal")
+    pos = _f32_frame(position, (H, W, 3), "position")
+    dist = _f32_frame(distance, (H, W), "distance")
+    obj = _f32_frame(object, (H, W), "object")
+    res = _denoise_out(rad, out)
+    uptr, _k = _host_ptr(rgb, H * W * 3, "rgb")
+    reg = None if region is None else _region(region)
+    opts = _denoise_options(levels, sigma_color, sigma_plane)
+    _lib.check(_lib.load().rt_denoise(W, H, C.byref(reg) if reg is not None else None, C.byref(opts), rad.ctypes.data,
+                                      nrm.ctypes.data, pos.ctypes.data, dist.ctypes.data, obj.ctypes.data,
+                                      res.ctypes.data, uptr))
+    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+
 class Camera:
     """The reference Camera (src/camera.ts:61-472), rendering on MI355X."""
 
@@ -289,6 +344,49 @@ class Camera:
         _lib.check(self._lib.rt_camera_progressive_restore(self._h, blob, len(blob)))
         return ProgressiveRender(self)
 
+    # -- guides and the denoised preview ------------------------------------------
+    def render_guides(self, region=None) -> dict:
+        """First-hit guide buffers (rt_camera_render_guides): one deterministic pinhole primary
+        ray per pixel of `region` (default: the whole image). Returns full-frame arrays
+        {"normal": float32 (H, W, 3), "position": float32 (H, W, 3), "distance": float32 (H, W),
+        "object": int32 (H, W): index in SceneData.objects, -1 on a miss}; pixels outside the
+        region hold zeros (object -1)."""
+        import numpy as np
+        H, W = self.image_height, self.image_width
+        g = {"normal": np.zeros((H, W, 3), np.float32), "position": np.zeros((H, W, 3), np.float32),
+             "distance": np.zeros((H, W), np.float32), "object": np.full((H, W), -1, np.int32)}
+        reg = None if region is None else _region(region)
+        _lib.check(self._lib.rt_camera_render_guides(self._h, C.byref(reg) if reg is not None else None,
+                                                     g["normal"].ctypes.data, g["position"].ctypes.data,
+                                                     g["distance"].ctypes.data, g["object"].ctypes.data))
+        return g
+
+    def denoise(self, radiance, region=None, *, levels=4, sigma_color=0.5, sigma_plane=0.01, rgb=None, out=None):
+        """rt_camera_denoise: the a-trous filter of a frame of this camera (float32 (H, W, 3), as
+        render_region's `radiance`), its guides computed on the device. Returns the filtered
+        radiance (H, W, 3) - a new array, or `out` (which may be `radiance` itself); `rgb`
+        (optional u8 W*H*3) receives the region's u8. Equals denoise(radiance,
+        **render_guides(region), region=region, ...)."""
+        H, W = self.image_height, self.image_width
+        rad = _f32_frame(radiance, (H, W, 3), "radiance")
+        res = _denoise_out(rad, out)
+        uptr, _k = _host_ptr(rgb, self.byte_length, "rgb")
+        reg = None if region is None else _region(region)
+        opts = _denoise_options(levels, sigma_color, sigma_plane)
+        _lib.check(self._lib.rt_camera_denoise(self._h, C.byref(reg) if reg is not None else None, C.byref(opts),
+                                               rad.ctypes.data, res.ctypes.data, uptr))
+        return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+    def denoise_times(self) -> dict:
+        """Device time of the last denoise / ProgressiveRender.denoised call, from HIP events
+        (rt_camera_denoise_times): guide pass ms (0 when a session reused its guides), ms of each
+        level, and the whole span guide pass .. filtered frame."""
+        n, g, t = C.c_int32(), C.c_float(), C.c_float()
+        lv = (C.c_float * _lib.DENOISE_MAX_LEVELS)()
+        _lib.check(self._lib.rt_camera_denoise_times(self._h, C.byref(n), C.byref(g), lv, C.byref(t)))
+        return {"levels": int(n.value), "guide_ms": float(g.value), "level_ms": [float(v) for v in lv][:n.value],
+                "total_ms": float(t.value)}
+
     def release_device(self) -> None:
         """Free the device copies; the next render re-creates them (rt_camera_release_device)."""
         _lib.check(self._lib.rt_camera_release_device(self._h))
@@ -364,6 +462,28 @@ class ProgressiveRender:
         st = _lib.RtRenderStats()
         _lib.check(cam._lib.rt_camera_progressive_step(cam._h, int(n), ptr, rptr, sptr, bptr, C.byref(st)))
         return RenderStats._from_c(st)
+
+    def denoised(self, buffer=None, radiance=None, *, levels=4, sigma_color=0.5, sigma_plane=0.01):
+        """The session's frame as it stands after the last step, through the a-trous filter
+        (rt_camera_progressive_denoise): the frame never leaves the device, the region's guides
+        are computed on first use and kept, and the session itself is not touched. `buffer` (u8
+        W*H*3) and `radiance` (float32 W*H*3) are optional caller-owned full-frame buffers; only
+        the region is written. Returns the filtered radiance as a (H, W, 3) array (`radiance`
+        when given; else a new one, zero outside the region)."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        import numpy as np
+        cam = self._cam
+        if radiance is None:
+            radiance = np.zeros((cam.image_height, cam.image_width, 3), np.float32)
+        ptr, _k0 = _host_ptr(buffer, cam.byte_length, "buffer")
+        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
+        opts = _denoise_options(levels, sigma_color, sigma_plane)
+        _lib.check(cam._lib.rt_camera_progressive_denoise(cam._h, C.byref(opts), ptr, rptr))
+        shape = (cam.image_height, cam.image_width, 3)
+        if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
+            return radiance.reshape(shape)
+        return radiance
 
     @property
     def info(self) -> dict:
