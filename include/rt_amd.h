@@ -454,6 +454,49 @@ int rt_camera_progressive_denoise(rt_camera* cam, const rt_denoise_options* opti
  * and the whole span guide pass .. filtered frame (host copies excluded). Waits for the events. */
 int rt_camera_denoise_times(rt_camera* cam, int32_t* levels, float* guide_ms, float* level_ms, float* total_ms);
 
+/* ---- Variance map and the variance-guided filter ---------------------------------------------
+ * Opt-in like the block above: no other call changes.
+ *
+ * Variance map. Per pixel of a progressive session's region, the variance of the pixel mean's
+ * illuminance (0.299 r + 0.587 g + 0.114 b, Color.illuminance) from the pixel's own running sums
+ * in fp64, in the reference's expression order (src/camera.ts:356-357), for n >= 2:
+ *     m2 = sumIll2 - (sumIll * sumIll) / n;   v = (m2 / (n - 1)) / n;   (float)(v > 0 ? v : 0)
+ * (NaN and negatives -> 0, n < 2 -> 0). Every pixel uses its own n: an adaptive pixel that
+ * retired early keeps the variance it retired with. `variance` is a HOST buffer in full-frame
+ * layout (width*height floats); only the region is written. rt_progressive_blob_variance
+ * evaluates the same formula on a checkpoint blob's payload on the host (no device; the blob is
+ * validated as rt_progressive_blob_info does; `variance` holds the blob's width*height floats).
+ * rt_camera_progressive_variance returns RT_ERR_INVALID without an open session, for a camera in
+ * mode bounces / samples and while samples_done < 2.
+ *
+ * Filter. The a-trous filter above with the colour edge-stop replaced and a variance channel
+ * carried along: `levels` passes at steps 1, 2, 4, ...; in each, the centre pixel's variance is
+ * pre-blurred (3x3, weights (1/4, 1/2, 1/4)^2 at unit spacing over the in-region pixels,
+ * normalised) to gv, k = 1 / (sigma_variance^2 gv + 1e-10), and a tap weighs
+ *     w = h max(0, n.n')^32 / ((1 + x^2) (1 + d^2 k)),   d = illuminance(tap) - illuminance(centre)
+ * with the plane term x, the hit / miss rule and the skipped taps of the filter above; then
+ * c' = sum(w c) / sum(w) and variance' = sum(w^2 variance) / sum(w)^2. The input variance is
+ * sanitised once (not (v >= 0 and finite) -> 0); a non-finite pixel keeps its colour and its
+ * variance. The result - colour and variance - equals the NumPy restatement
+ * tests/denoise_var_ref.py (the normative definition) in every bit. Buffers and errors as above
+ * (HOST buffers, full-frame layout, only the region read and written, outputs may be NULL);
+ * variance_out may be variance. rt_camera_progressive_denoise_variance filters the open session's
+ * device frame with the variance of its state and its kept guides, touches neither state nor
+ * frame, and also returns RT_ERR_INVALID while samples_done < 2. rt_camera_denoise_times reports
+ * these calls too; for the session call its guide_ms span includes the variance pass. */
+typedef struct { int32_t levels; float sigma_variance, sigma_plane; } rt_denoise_var_options;   /* NULL or a zero field = default (4, 2.0, 0.01) */
+int rt_progressive_blob_variance(const uint8_t* blob, size_t len, float* variance);
+int rt_camera_progressive_variance(rt_camera* cam, float* variance);
+int rt_denoise_variance(int32_t width, int32_t height, const rt_region* region, const rt_denoise_var_options* options,
+                        const float* radiance, const float* variance, const float* normal, const float* position,
+                        const float* distance, const int32_t* object, float* radiance_out, float* variance_out,
+                        uint8_t* rgb_out);
+int rt_camera_denoise_variance(rt_camera* cam, const rt_region* region, const rt_denoise_var_options* options,
+                               const float* radiance, const float* variance, float* radiance_out, float* variance_out,
+                               uint8_t* rgb_out);
+int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_options* options, uint8_t* rgb,
+                                           float* radiance, float* variance_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@
 
 #include "../../include/rt_amd.h"
 #include "denoise.hpp"
+#include "denoise_var.hpp"
 #include "json.hpp"
 #include "launch.hpp"
 #include "progressive.hpp"
@@ -145,15 +146,26 @@ struct DnBufs {
     int32_t* obj = nullptr;
     uint8_t* u8 = nullptr;
     size_t cap = 0;  // pixels
+    float* var = nullptr;  // region-packed variance of the variance-guided calls (denoise_var.hpp)
+    size_t var_cap = 0;
     float* rad() const { return stage; }
     float* nrm() const { return stage + 3 * cap; }
     float* pos() const { return stage + 6 * cap; }
     float* dist() const { return stage + 9 * cap; }
     // (the caller has made the buffers' device current)
     void free() {
-        for (void* p : {(void*)c0, (void*)c1, (void*)fn, (void*)gn, (void*)gp, (void*)stage, (void*)obj, (void*)u8})
+        for (void* p : {(void*)c0, (void*)c1, (void*)fn, (void*)gn, (void*)gp, (void*)stage, (void*)obj, (void*)u8,
+                        (void*)var})
             if (p) (void)hipFree(p);
         *this = DnBufs{};
+    }
+    void ensure_var(size_t n) {
+        if (n <= var_cap) return;
+        if (var) (void)hipFree(var);
+        var = nullptr;
+        var_cap = 0;
+        hip_check(hipMalloc(&var, n * sizeof(float)), "hipMalloc(denoise variance)");
+        var_cap = n;
     }
     void ensure(size_t n) {
         if (n <= cap) return;
@@ -241,6 +253,54 @@ static void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float
     }
     hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8 : nullptr, stream),
               "denoise_unpack_kernel");
+    mark();
+}
+
+// rt_denoise_var_options resolved: NULL or a zero field = the default.
+struct DnvOpts {
+    int32_t levels = 4;
+    float sigma_variance = 2.0f, sigma_plane = 0.01f;
+};
+static DnvOpts dnv_options(const rt_denoise_var_options* o, const std::string& who) {
+    DnvOpts r;
+    if (!o) return r;
+    if (o->levels < 0 || o->levels > kDenoiseMaxLevels)
+        throw std::invalid_argument(who + ": levels must be 1.." + std::to_string(kDenoiseMaxLevels) + " (0: the default)");
+    if (!(o->sigma_variance >= 0.0f) || !std::isfinite(o->sigma_variance))
+        throw std::invalid_argument(who + ": sigma_variance must be positive and finite (0: the default)");
+    if (!(o->sigma_plane >= 0.0f) || !std::isfinite(o->sigma_plane))
+        throw std::invalid_argument(who + ": sigma_plane must be positive and finite (0: the default)");
+    if (o->levels) r.levels = o->levels;
+    if (o->sigma_variance != 0.0f) r.sigma_variance = o->sigma_variance;
+    if (o->sigma_plane != 0.0f) r.sigma_plane = o->sigma_plane;
+    return r;
+}
+
+// The variance-guided filter (denoise_var.hpp), as dn_filter: the colour's w carries the
+// region-packed variance b.var, which receives the filtered variance when want_var. Events as
+// dn_filter's (the variance unpack falls into the last span). Queued.
+static void dnv_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0,
+                       int w, int h, const DnvOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream,
+                       hipEvent_t* ev) {
+    int e = 0;
+    auto mark = [&] {
+        if (ev) hip_check(hipEventRecord(ev[e++], stream), "hipEventRecord");
+    };
+    mark();
+    hip_check(launch_denoise_var_pack(rad, pitch_px, x0, y0, w, h, gn, o.sigma_plane, b.var, b.c0, b.fn, stream),
+              "denoise_var_pack_kernel");
+    mark();
+    // sigma_variance^2: in double on the host, rounded to fp32 once
+    const float s2 = (float)((double)o.sigma_variance * (double)o.sigma_variance);
+    float4 *src = b.c0, *dst = b.c1;
+    for (int lv = 0; lv < o.levels; ++lv) {
+        hip_check(launch_denoise_var_level(src, dst, b.fn, gp, w, h, 1 << lv, s2, stream), "denoise_var kernel");
+        mark();
+        std::swap(src, dst);
+    }
+    hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8 : nullptr, stream),
+              "denoise_unpack_kernel");
+    if (want_var) hip_check(launch_denoise_var_unpack(src, w * h, b.var, stream), "denoise_var_unpack_kernel");
     mark();
 }
 
@@ -2317,6 +2377,32 @@ int rt_progressive_blob_info(const uint8_t* blob, size_t len, rt_progressive_inf
     }
 }
 
+int rt_progressive_blob_variance(const uint8_t* blob, size_t len, float* variance) {
+    if (!variance) return set_error(RT_ERR_INVALID, "null argument");
+    try {
+        const ProgBlobHeader h = prog_parse_blob(blob, len);
+        if (h.width <= 0 || h.height <= 0 || h.rx < 0 || h.ry < 0 || (long)h.rx + h.rw > h.width ||
+            (long)h.ry + h.rh > h.height)
+            throw std::invalid_argument("progressive blob: corrupt header (the region does not fit the image)");
+        // the payload by slot = region tile * 64 + lane (the kernels' item_pixel numbering)
+        const int tiles_x = (h.rw + kTile - 1) / kTile;
+        const long slots = (long)(h.payload_bytes / sizeof(ProgPix));
+        for (long slot = 0; slot < slots; ++slot) {
+            const int tile = (int)(slot / kWave), lane = (int)(slot % kWave);
+            const int ty = tile / tiles_x;
+            const int i = h.rx + (tile - ty * tiles_x) * kTile + (lane & (kTile - 1));
+            const int j = h.ry + ty * kTile + lane / kTile;
+            if (i >= h.rx + h.rw || j >= h.ry + h.rh) continue;
+            ProgPix p;
+            std::memcpy(&p, blob + sizeof h + (size_t)slot * sizeof p, sizeof p);
+            variance[(size_t)j * h.width + i] = prog_variance(p.ill.x, p.ill.y, prog_pix_samples(p));
+        }
+        return RT_OK;
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_INVALID, e.what());
+    }
+}
+
 int rt_camera_progressive_end(rt_camera* cam) {
     return camera_call(cam, [&] { cam->end_session(); });
 }
@@ -2442,6 +2528,156 @@ int rt_camera_progressive_denoise(rt_camera* cam, const rt_denoise_options* opti
         dn_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, r.x, r.y, r.width, r.height, o, radiance != nullptr, rgb != nullptr,
                   stream, ev + 1);
         dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(rgb, b.u8, 3, C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+// ---- Variance map and the variance-guided filter (denoise_var.hpp) -----------------------------
+// The open session whose state holds a variance: mode default and two samples or more. Argument
+// errors first, then the device check.
+static DevCtx& variance_session(rt_camera* cam, const std::string& who) {
+    DevCtx& c = cam->session(who.c_str());
+    if (cam->build.cam.mode != MODE_DEFAULT)
+        throw std::invalid_argument(who + ": the frames of mode bounces / samples are not radiance");
+    if (c.prog.done < 2)
+        throw std::invalid_argument(who + ": a variance needs at least 2 samples per pixel, the session has " +
+                                    std::to_string(c.prog.done) + " (samples_done < 2)");
+    int dev = 0;
+    hip_check(hipGetDevice(&dev), "hipGetDevice");
+    if (dev != c.device) throw std::invalid_argument(who + ": the session lives on another device");
+    return c;
+}
+
+// The session's state -> b.var (region-packed); queued.
+static void prog_variance_pass(DevCtx& c, hipStream_t stream) {
+    DevCtx::ProgSession& P = c.prog;
+    c.dn.ensure_var((size_t)P.region.width * P.region.height);
+    const int tiles_x = std::max((P.region.width + kTile - 1) / kTile, 1);
+    hip_check(launch_prog_variance(P.d_state, (int)P.slots, c.prog_reg(), tiles_x, c.dn.var, stream),
+              "prog_variance_kernel");
+}
+
+int rt_camera_progressive_variance(rt_camera* cam, float* variance) {
+    return camera_call(cam, [&] {
+        if (!variance) throw std::invalid_argument("rt_camera_progressive_variance: variance is required");
+        DevCtx& c = variance_session(cam, "rt_camera_progressive_variance");
+        const hipStream_t stream = nullptr;
+        prog_variance_pass(c, stream);
+        dn_download(variance, c.dn.var, sizeof(float), cam->build.cam.width, c.prog.region, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_denoise_variance(int32_t width, int32_t height, const rt_region* region, const rt_denoise_var_options* options,
+                        const float* radiance, const float* variance, const float* normal, const float* position,
+                        const float* distance, const int32_t* object, float* radiance_out, float* variance_out,
+                        uint8_t* rgb_out) {
+    DnBufs b;
+    int rc = RT_OK;
+    try {
+        if (width <= 0 || height <= 0) throw std::invalid_argument("rt_denoise_variance: width and height must be positive");
+        if (!radiance || !variance || !normal || !position || !distance || !object)
+            throw std::invalid_argument(
+                "rt_denoise_variance: radiance, variance, normal, position, distance and object are required");
+        const DnvOpts o = dnv_options(options, "rt_denoise_variance");
+        const rt_region r = dn_region(region, width, height, "rt_denoise_variance");
+        const hipStream_t stream = nullptr;
+        const int n = r.width * r.height;
+        b.ensure((size_t)n);
+        b.ensure_var((size_t)n);
+        dn_upload(b.rad(), radiance, 3 * sizeof(float), width, r, stream);
+        dn_upload(b.var, variance, sizeof(float), width, r, stream);
+        dn_upload(b.nrm(), normal, 3 * sizeof(float), width, r, stream);
+        dn_upload(b.pos(), position, 3 * sizeof(float), width, r, stream);
+        dn_upload(b.dist(), distance, sizeof(float), width, r, stream);
+        dn_upload(b.obj, object, sizeof(int32_t), width, r, stream);
+        const DenoiseGuides g{b.gn, b.gp};
+        hip_check(launch_guides_pack(g, n, b.nrm(), b.pos(), b.dist(), b.obj, stream), "guides_pack_kernel");
+        dnv_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
+                   rgb_out != nullptr, variance_out != nullptr, stream, nullptr);
+        dn_download(radiance_out, b.rad(), 3 * sizeof(float), width, r, stream);
+        dn_download(variance_out, b.var, sizeof(float), width, r, stream);
+        dn_download(rgb_out, b.u8, 3, width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    } catch (const HipError& e) {
+        rc = set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        rc = set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        rc = set_error(RT_ERR_RENDER, e.what());
+    }
+    b.free();
+    return rc;
+}
+
+int rt_camera_denoise_variance(rt_camera* cam, const rt_region* region, const rt_denoise_var_options* options,
+                               const float* radiance, const float* variance, float* radiance_out, float* variance_out,
+                               uint8_t* rgb_out) {
+    return camera_call(cam, [&] {
+        const RtCamera& C = cam->build.cam;
+        if (!radiance || !variance)
+            throw std::invalid_argument("rt_camera_denoise_variance: radiance and variance are required");
+        const DnvOpts o = dnv_options(options, "rt_camera_denoise_variance");
+        const rt_region r = dn_region(region, C.width, C.height, "rt_camera_denoise_variance");
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        const hipStream_t stream = nullptr;
+        DnBufs& b = c.dn;
+        b.ensure((size_t)r.width * r.height);
+        b.ensure_var((size_t)r.width * r.height);
+        hipEvent_t* ev = c.dn_events(o.levels);
+        dn_upload(b.rad(), radiance, 3 * sizeof(float), C.width, r, stream);
+        dn_upload(b.var, variance, sizeof(float), C.width, r, stream);
+        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+        c.launch_guide_pass(r, cam->traversal, DenoiseGuides{b.gn, b.gp}, stream);
+        c.dn_guides = true;
+        dnv_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
+                   rgb_out != nullptr, variance_out != nullptr, stream, ev + 1);
+        dn_download(radiance_out, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
+        dn_download(rgb_out, b.u8, 3, C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_options* options, uint8_t* rgb,
+                                           float* radiance, float* variance_out) {
+    return camera_call(cam, [&] {
+        const std::string who = "rt_camera_progressive_denoise_variance";
+        const RtCamera& C = cam->build.cam;
+        // (the options before the session's sample count: every argument error needs no device)
+        (void)cam->session(who.c_str());
+        const DnvOpts o = dnv_options(options, who);
+        DevCtx& c = variance_session(cam, who);
+        DevCtx::ProgSession& P = c.prog;
+        const rt_region r = P.region;
+        const hipStream_t stream = nullptr;
+        const size_t n = (size_t)r.width * r.height;
+        DnBufs& b = c.dn;
+        b.ensure(n);
+        b.ensure_var(n);
+        hipEvent_t* ev = c.dn_events(o.levels);
+        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+        c.dn_guides = true;  // the span [0, 1): the variance pass, after the guide pass of a first call
+        if (!P.d_gn) {  // the region's guides: computed once, freed with the session
+            try {
+                hip_check(hipMalloc(&P.d_gn, n * sizeof(float4)), "hipMalloc(session guides)");
+                hip_check(hipMalloc(&P.d_gp, n * sizeof(float4)), "hipMalloc(session guides)");
+                c.launch_guide_pass(r, cam->traversal, DenoiseGuides{P.d_gn, P.d_gp}, stream);
+            } catch (...) {
+                if (P.d_gn) (void)hipFree(P.d_gn);
+                if (P.d_gp) (void)hipFree(P.d_gp);
+                P.d_gn = P.d_gp = nullptr;
+                throw;
+            }
+        }
+        prog_variance_pass(c, stream);
+        // the session's device frame and state as they stand after the last step: nothing is uploaded
+        dnv_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, r.x, r.y, r.width, r.height, o, radiance != nullptr, rgb != nullptr,
+                   variance_out != nullptr, stream, ev + 1);
+        dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
         dn_download(rgb, b.u8, 3, C.width, r, stream);
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     });

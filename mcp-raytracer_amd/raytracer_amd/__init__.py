@@ -12,9 +12,11 @@ This package is the host-side mirror of the reference's TypeScript surface:
 plus progressive rendering, which the reference lacks: Camera.progressive / Camera.resume ->
 ProgressiveRender (resumable sample steps with a preview and checkpoints), and first-hit
 guide buffers with a guided edge-avoiding a-trous filter for low-sample frames:
-Camera.render_guides / Camera.denoise / denoise / ProgressiveRender.denoised.
+Camera.render_guides / Camera.denoise / denoise / ProgressiveRender.denoised; a session's
+per-pixel variance map (ProgressiveRender.variance, progressive_blob_variance) guides that filter
+when `variance=` is passed to any of them.
 """
-from ._lib import RtError, build_id, device_count, progressive_blob_info
+from ._lib import RtError, build_id, device_count, progressive_blob_info, progressive_blob_variance
 from .camera import Camera, ProgressiveRender, RenderStats, denoise, rng_stream
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
@@ -22,7 +24,7 @@ from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, g
 
 __all__ = [
     "Camera", "ProgressiveRender", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
-    "progressive_blob_info", "denoise",
+    "progressive_blob_info", "progressive_blob_variance", "denoise",
     "generate_scene_data", "create_camera_from_scene_data", "generate_scene",
     "generate_image_buffer", "divide_into_regions",
     "generateSceneData", "createCameraFromSceneData", "generateScene", "generateImageBuffer",

@@ -50,6 +50,9 @@ _UNITS = [
     # guide pass + a-trous filter: every fp32 operation must round once (no contraction; plain /
     # and sqrtf are IEEE under hipcc's defaults) - the output equals tests/denoise_ref.py in every bit
     ("denoise.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # variance map + variance-guided filter: as denoise.hip (tests/denoise_var_ref.py); the fp64
+    # variance formula is also evaluated on the host in rt_api.cpp, which never contracts either
+    ("denoise_var.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     ("frame.hip", [], True),
     ("png.hip", [], True),
     ("rt_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
@@ -57,6 +60,7 @@ _UNITS = [
     ("image.cpp", [], False),
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
+            "denoise_var.hpp",
             "png_deflate.hpp"]
 _LIBS = ["-lz"]
 

@@ -94,6 +94,10 @@ class RtDenoiseOptions(C.Structure):
     _fields_ = [("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_plane", C.c_float)]
 
 
+class RtDenoiseVarOptions(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("sigma_variance", C.c_float), ("sigma_plane", C.c_float)]
+
+
 DENOISE_MAX_LEVELS = 8
 
 
@@ -170,6 +174,15 @@ _SIGS = {
     "rt_camera_progressive_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseOptions), C.c_void_p, C.c_void_p]),
     "rt_camera_denoise_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                           C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "rt_progressive_blob_variance": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p]),
+    "rt_camera_progressive_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_denoise_variance": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.POINTER(RtDenoiseVarOptions),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.POINTER(RtDenoiseVarOptions),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_progressive_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseVarOptions), C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -247,6 +260,19 @@ def progressive_blob_info(blob: bytes) -> dict:
     blob = bytes(blob)
     check(load().rt_progressive_blob_info(blob, len(blob), C.byref(info)))
     return info.as_dict()
+
+
+def progressive_blob_variance(blob: bytes):
+    """rt_progressive_blob_variance: the per-pixel variance of the pixel mean's illuminance held
+    by a checkpoint blob, on the host (no device) - a float32 (height, width) array, zero outside
+    the blob's region. Equals ProgressiveRender.variance() of the session that saved it. Raises
+    RtError on a bad blob."""
+    import numpy as np
+    blob = bytes(blob)
+    info = progressive_blob_info(blob)
+    var = np.zeros((info["height"], info["width"]), np.float32)
+    check(load().rt_progressive_blob_variance(blob, len(blob), var.ctypes.data))
+    return var
 
 
 def device_count() -> int:

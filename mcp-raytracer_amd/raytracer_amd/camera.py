@@ -88,6 +88,30 @@ def _denoise_options(levels, sigma_color, sigma_plane) -> _lib.RtDenoiseOptions:
     return _lib.RtDenoiseOptions(int(levels), float(sigma_color), float(sigma_plane))
 
 
+def _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane):
+    """Which filter a denoise call runs. Without `variance`: (False, rt_denoise_options) - the
+    colour edge-stop, sigma_color 0.5 unless given. With it: (True, rt_denoise_var_options)."""
+    if variance is None or variance is False:
+        if variance_out is not None:
+            raise ValueError("variance_out needs variance=")
+        return False, _denoise_options(levels, 0.5 if sigma_color is None else sigma_color, sigma_plane)
+    if sigma_color is not None:
+        raise ValueError("sigma_color belongs to the colour edge-stop: pass either sigma_color or variance=, not both")
+    return True, _lib.RtDenoiseVarOptions(int(levels), float(sigma_variance), float(sigma_plane))
+
+
+def _var_out(variance_out, shape):
+    """Pointer of the optional caller-owned (H, W) float32 array the filtered variance goes to."""
+    import numpy as np
+    if variance_out is None:
+        return None
+    if (not isinstance(variance_out, np.ndarray) or variance_out.dtype != np.float32
+            or not variance_out.flags["C_CONTIGUOUS"] or not variance_out.flags["WRITEABLE"]
+            or variance_out.size != shape[0] * shape[1]):
+        raise ValueError("variance_out must be a writable C-contiguous float32 array of H*W values")
+    return variance_out.ctypes.data
+
+
 def _f32_frame(a, shape, what: str):
     """`a` as a C-contiguous float32 / int32 array of `shape` (no copy when it already is)."""
     import numpy as np
@@ -110,14 +134,20 @@ def _denoise_out(src, out):
     return out
 
 
-def denoise(radiance, normal, position, distance, object, region=None, *, levels=4, sigma_color=0.5,
-            sigma_plane=0.01, rgb=None, out=None):
+def denoise(radiance, normal, position, distance, object, region=None, *, levels=4, sigma_color=None,
+            sigma_plane=0.01, rgb=None, out=None, variance=None, sigma_variance=2.0, variance_out=None):
     """rt_denoise: the guided edge-avoiding a-trous filter of a frame with explicit guides (as
     Camera.render_guides returns them), no camera. radiance / normal / position: float32
     (H, W, 3); distance float32, object int32: (H, W). Returns the filtered radiance (H, W, 3) -
     a new array, or `out` (which may be `radiance` itself); only the region is filtered. `rgb`
     (optional caller-owned u8 H*W*3) receives the region's u8. Equals tests/denoise_ref.py in
-    every bit."""
+    every bit. sigma_color defaults to 0.5.
+
+    `variance` (float32 (H, W): the variance of each pixel's mean illuminance, as
+    ProgressiveRender.variance returns it) selects the variance-guided filter
+    (rt_denoise_variance, tests/denoise_var_ref.py) with `sigma_variance` in place of
+    sigma_color; `variance_out` (optional float32 (H, W)) then receives the region's filtered
+    variance. Passing sigma_color together with variance raises ValueError."""
     import numpy as np
     rad = np.asarray(radiance)
     if rad.ndim != 3 or rad.shape[2] != 3:
@@ -131,10 +161,16 @@ def denoise(radiance, normal, position, distance, object, region=None, *, levels
     res = _denoise_out(rad, out)
     uptr, _k = _host_ptr(rgb, H * W * 3, "rgb")
     reg = None if region is None else _region(region)
-    opts = _denoise_options(levels, sigma_color, sigma_plane)
-    _lib.check(_lib.load().rt_denoise(W, H, C.byref(reg) if reg is not None else None, C.byref(opts), rad.ctypes.data,
-                                      nrm.ctypes.data, pos.ctypes.data, dist.ctypes.data, obj.ctypes.data,
-                                      res.ctypes.data, uptr))
+    guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
+    rptr = C.byref(reg) if reg is not None else None
+    if guided:
+        var = _f32_frame(variance, (H, W), "variance")
+        _lib.check(_lib.load().rt_denoise_variance(W, H, rptr, C.byref(opts), rad.ctypes.data, var.ctypes.data,
+                                                   nrm.ctypes.data, pos.ctypes.data, dist.ctypes.data, obj.ctypes.data,
+                                                   res.ctypes.data, _var_out(variance_out, (H, W)), uptr))
+    else:
+        _lib.check(_lib.load().rt_denoise(W, H, rptr, C.byref(opts), rad.ctypes.data, nrm.ctypes.data, pos.ctypes.data,
+                                          dist.ctypes.data, obj.ctypes.data, res.ctypes.data, uptr))
     return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
 
 
@@ -361,20 +397,30 @@ class Camera:
                                                      g["distance"].ctypes.data, g["object"].ctypes.data))
         return g
 
-    def denoise(self, radiance, region=None, *, levels=4, sigma_color=0.5, sigma_plane=0.01, rgb=None, out=None):
+    def denoise(self, radiance, region=None, *, levels=4, sigma_color=None, sigma_plane=0.01, rgb=None, out=None,
+                variance=None, sigma_variance=2.0, variance_out=None):
         """rt_camera_denoise: the a-trous filter of a frame of this camera (float32 (H, W, 3), as
         render_region's `radiance`), its guides computed on the device. Returns the filtered
         radiance (H, W, 3) - a new array, or `out` (which may be `radiance` itself); `rgb`
         (optional u8 W*H*3) receives the region's u8. Equals denoise(radiance,
-        **render_guides(region), region=region, ...)."""
+        **render_guides(region), region=region, ...). `variance` (float32 (H, W)), `sigma_variance`
+        and `variance_out` select the variance-guided filter (rt_camera_denoise_variance) as in
+        denoise()."""
         H, W = self.image_height, self.image_width
         rad = _f32_frame(radiance, (H, W, 3), "radiance")
         res = _denoise_out(rad, out)
         uptr, _k = _host_ptr(rgb, self.byte_length, "rgb")
         reg = None if region is None else _region(region)
-        opts = _denoise_options(levels, sigma_color, sigma_plane)
-        _lib.check(self._lib.rt_camera_denoise(self._h, C.byref(reg) if reg is not None else None, C.byref(opts),
-                                               rad.ctypes.data, res.ctypes.data, uptr))
+        guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
+        rptr = C.byref(reg) if reg is not None else None
+        if guided:
+            var = _f32_frame(variance, (H, W), "variance")
+            _lib.check(self._lib.rt_camera_denoise_variance(self._h, rptr, C.byref(opts), rad.ctypes.data,
+                                                            var.ctypes.data, res.ctypes.data,
+                                                            _var_out(variance_out, (H, W)), uptr))
+        else:
+            _lib.check(self._lib.rt_camera_denoise(self._h, rptr, C.byref(opts), rad.ctypes.data, res.ctypes.data,
+                                                   uptr))
         return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
 
     def denoise_times(self) -> dict:
@@ -463,13 +509,34 @@ class ProgressiveRender:
         _lib.check(cam._lib.rt_camera_progressive_step(cam._h, int(n), ptr, rptr, sptr, bptr, C.byref(st)))
         return RenderStats._from_c(st)
 
-    def denoised(self, buffer=None, radiance=None, *, levels=4, sigma_color=0.5, sigma_plane=0.01):
+    def variance(self, out=None):
+        """The per-pixel variance of the pixel mean's illuminance from the session's running sums
+        (rt_camera_progressive_variance): a float32 (H, W) array - `out` when given, else a new
+        one, zero outside the region. Every pixel uses its own sample count. Needs
+        samples_done >= 2 and a camera in the default mode."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        import numpy as np
+        cam = self._cam
+        shape = (cam.image_height, cam.image_width)
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        ptr = _var_out(out, shape)
+        _lib.check(cam._lib.rt_camera_progressive_variance(cam._h, ptr))
+        return out if out.shape == shape else out.reshape(shape)
+
+    def denoised(self, buffer=None, radiance=None, *, levels=4, sigma_color=None, sigma_plane=0.01, variance=False,
+                 sigma_variance=2.0, variance_out=None):
         """The session's frame as it stands after the last step, through the a-trous filter
         (rt_camera_progressive_denoise): the frame never leaves the device, the region's guides
         are computed on first use and kept, and the session itself is not touched. `buffer` (u8
         W*H*3) and `radiance` (float32 W*H*3) are optional caller-owned full-frame buffers; only
         the region is written. Returns the filtered radiance as a (H, W, 3) array (`radiance`
-        when given; else a new one, zero outside the region)."""
+        when given; else a new one, zero outside the region). `variance=True` runs the
+        variance-guided filter on the variance of the session's own state
+        (rt_camera_progressive_denoise_variance; needs samples_done >= 2) with `sigma_variance`
+        in place of sigma_color; `variance_out` (optional float32 (H, W)) receives the region's
+        filtered variance."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
         import numpy as np
@@ -478,8 +545,12 @@ class ProgressiveRender:
             radiance = np.zeros((cam.image_height, cam.image_width, 3), np.float32)
         ptr, _k0 = _host_ptr(buffer, cam.byte_length, "buffer")
         rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
-        opts = _denoise_options(levels, sigma_color, sigma_plane)
-        _lib.check(cam._lib.rt_camera_progressive_denoise(cam._h, C.byref(opts), ptr, rptr))
+        guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
+        if guided:
+            vptr = _var_out(variance_out, (cam.image_height, cam.image_width))
+            _lib.check(cam._lib.rt_camera_progressive_denoise_variance(cam._h, C.byref(opts), ptr, rptr, vptr))
+        else:
+            _lib.check(cam._lib.rt_camera_progressive_denoise(cam._h, C.byref(opts), ptr, rptr))
         shape = (cam.image_height, cam.image_width, 3)
         if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
             return radiance.reshape(shape)
