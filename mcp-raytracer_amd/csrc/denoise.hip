@@ -2,7 +2,8 @@
 // fast-math, denormal-flushing or approximate-reciprocal flag: every fp32 operation of the
 // filter (add, multiply, IEEE divide, max, repeated squaring) and of the guide distance
 // (correctly rounded sqrtf) has exactly one result, and the tap order and the
-// multiply-then-add accumulation are part of it - tests/denoise_ref.py is the definition.
+// multiply-then-add accumulation are part of it - tests/denoise_ref.py is the definition, and
+// tests/denoise_var_ref.py that of the variance-guided form.
 #include "denoise.hpp"
 
 #include <algorithm>
@@ -85,25 +86,53 @@ __global__ __launch_bounds__(kDnBlock) void guides_pack_kernel(DenoiseGuides g, 
 }
 
 // ---- filter -----------------------------------------------------------------------------------
+// One filter, two forms chosen at compile time (VAR: the variance-guided one). They differ in
+// the colour weight, in the variance lane (pre-blur, accumulation, divide) and in what colour.w
+// holds - the helpers below and the `if constexpr (VAR)` lines; everything else is written once.
 __device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
+// colour.w. Plain: the finite flag, 1.0f / 0.0f. VAR: the variance, its sign bit set when the
+// colour is not finite.
+constexpr uint32_t kDnFlag = 0x80000000u;
+template <bool VAR>
+__device__ __forceinline__ bool dn_is_finite(const float4& c) {
+    if constexpr (VAR) return (__float_as_uint(c.w) & kDnFlag) == 0u;
+    else return c.w != 0.0f;
+}
+__device__ __forceinline__ float dn_var(const float4& c) { return __uint_as_float(__float_as_uint(c.w) & ~kDnFlag); }
+template <bool VAR>
+__device__ __forceinline__ float dn_pack_w(float v, bool finite) {
+    if constexpr (VAR) return __uint_as_float((__float_as_uint(v) & ~kDnFlag) | (finite ? 0u : kDnFlag));
+    else return finite ? 1.0f : 0.0f;
+}
+// Color.illuminance of a colour, in the definition's order
+__device__ __forceinline__ float dn_lum(const float4& c) { return (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z; }
+
+template <bool VAR>
 __global__ __launch_bounds__(kDnBlock) void denoise_pack_kernel(const float* rad, int pitch_px, int x0, int y0, int w,
                                                                  int h, const float4* gn, float sigma_plane,
-                                                                 float4* colour, float4* fn) {
+                                                                 float4* colour, float4* fn, const float* variance) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= w * h) return;
     const int y = k / w, x = k - y * w;
     const float* s = rad + 3 * ((size_t)(y0 + y) * (size_t)pitch_px + (size_t)(x0 + x));
     const float r = s[0], g = s[1], b = s[2];
-    colour[k] = make_float4(r, g, b, finite_f(r) && finite_f(g) && finite_f(b) ? 1.0f : 0.0f);
+    float vs = 0.0f;
+    if constexpr (VAR) {
+        const float v = variance[k];
+        vs = v >= 0.0f && finite_f(v) ? v : 0.0f;  // sanitised once: NaN, negatives and inf -> 0
+    }
+    colour[k] = make_float4(r, g, b, dn_pack_w<VAR>(vs, finite_f(r) && finite_f(g) && finite_f(b)));
     const float4 a = gn[k];
     fn[k] = make_float4(a.x, a.y, a.z, 1.0f / (sigma_plane * a.w));
 }
 
-__global__ __launch_bounds__(kDnBlock) void denoise_unpack_kernel(const float4* colour, int n, float* rad, uint8_t* rgb) {
+__global__ __launch_bounds__(kDnBlock) void denoise_unpack_kernel(const float4* colour, int n, float* rad, uint8_t* rgb,
+                                                                   float* variance) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const float4 c = colour[k];
+    if (variance) variance[k] = dn_var(c);
     if (rad) {
         rad[3 * (size_t)k] = c.x;
         rad[3 * (size_t)k + 1] = c.y;
@@ -116,20 +145,53 @@ __global__ __launch_bounds__(kDnBlock) void denoise_unpack_kernel(const float4* 
     }
 }
 
-// The B3 spline's taps (exact in fp32, and so are their products).
+// The B3 spline's taps and the pre-blur's (1/4, 1/2, 1/4): exact in fp32, and so are their products.
 __device__ __forceinline__ float h5(int k) {
     return k == 2 ? 0.375f : (k == 1 || k == 3) ? 0.25f : 0.0625f;
 }
+__device__ __forceinline__ float h3(int k) { return k == 1 ? 0.5f : 0.25f; }
 
+// A pixel's weighted sums. The plain form has no variance lane at all: a dead one is removed
+// but still renumbers the kernel's registers.
+template <bool VAR>
 struct DnSum {
     float r, g, b, w;
 };
+template <>
+struct DnSum<true> {
+    float r, g, b, w, v;
+};
 
-// One tap of pixel p (colour cp, guides np / pp, finite flag finp, miss flag missp) at pixel q,
-// in the definition's operation order.
-__device__ __forceinline__ void dn_tap(const float4& cp, const float4& np, const float4& pp, bool finp, bool missp,
-                                       const float4& cq, const float4& nq, const float4& pq, float hk, float k_c,
-                                       DnSum& s) {
+// The centre pixel's part of the colour weight. Plain: nothing, the launch's k_c = 4^level /
+// sigma_color^2 is the falloff. VAR: its luminance, and k_p = 1 / (s2 * gv + 1e-10f), gv the
+// 3x3 (1/4, 1/2, 1/4) blur of the variance around it; var_at(dx, dy) reads a neighbour's
+// variance, and neighbours outside the region are skipped.
+struct DnCentre {
+    float lum, k;
+};
+template <class VarAt>
+__device__ __forceinline__ DnCentre dn_centre(const float4& cp, int px, int py, int w, int h, float s2, VarAt var_at) {
+    float sv = 0.0f, sw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = px + dx, qy = py + dy;
+            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+            const float hk = h3(dy + 1) * h3(dx + 1);
+            sv = sv + hk * var_at(dx, dy);
+            sw = sw + hk;
+        }
+    }
+    return DnCentre{dn_lum(cp), 1.0f / (s2 * (sv / sw) + 1e-10f)};
+}
+
+// One tap of pixel p (colour cp, centre part ce, guides np / pp, finite flag finp, miss flag
+// missp) at pixel q, in the definition's operation order.
+template <bool VAR>
+__device__ __forceinline__ void dn_tap(const float4& cp, const DnCentre& ce, const float4& np, const float4& pp, bool finp,
+                                       bool missp, const float4& cq, const float4& nq, const float4& pq, float hk,
+                                       DnSum<VAR>& s) {
     float dn = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
     dn = dn < 0.0f ? 0.0f : dn;  // max(dn, 0), a NaN kept
     dn = dn * dn;
@@ -140,42 +202,53 @@ __device__ __forceinline__ void dn_tap(const float4& cp, const float4& np, const
     const float dpx = pq.x - pp.x, dpy = pq.y - pp.y, dpz = pq.z - pp.z;
     const float e = (np.x * dpx + np.y * dpy) + np.z * dpz;
     const float x = e * np.w;
-    const float dcx = cq.x - cp.x, dcy = cq.y - cp.y, dcz = cq.z - cp.z;
-    const float y = (dcx * dcx + dcy * dcy) + dcz * dcz;
-    const float cw = 1.0f + y * k_c;
+    float cw;
+    if constexpr (VAR) {  // the luminance difference against the centre's own variance
+        const float d = dn_lum(cq) - ce.lum;
+        cw = 1.0f + (d * d) * ce.k;
+    } else {  // the RGB distance
+        const float dcx = cq.x - cp.x, dcy = cq.y - cp.y, dcz = cq.z - cp.z;
+        const float y = (dcx * dcx + dcy * dcy) + dcz * dcz;
+        cw = 1.0f + y * ce.k;
+    }
     const bool missq = __float_as_int(pq.w) < 0;
     // two misses: the colour weight only; a hit and a miss never mix. One IEEE division.
     const bool both = missp && missq;
     const float num = both ? hk : hk * dn;
     const float den = both ? cw : (1.0f + x * x) * cw;
     const float wq = num / den;
-    const bool ok = finp && cq.w != 0.0f;  // non-finite taps are skipped
+    const bool ok = finp && dn_is_finite<VAR>(cq);  // non-finite taps are skipped
     const float wt = ok && missp == missq ? wq : 0.0f;
     s.r = s.r + wt * (ok ? cq.x : 0.0f);
     s.g = s.g + wt * (ok ? cq.y : 0.0f);
     s.b = s.b + wt * (ok ? cq.z : 0.0f);
     s.w = s.w + wt;
+    if constexpr (VAR) s.v = s.v + (wt * wt) * (ok ? dn_var(cq) : 0.0f);
 }
 
-__device__ __forceinline__ float4 dn_finish(const float4& cp, bool finp, const DnSum& s) {
+template <bool VAR>
+__device__ __forceinline__ float4 dn_finish(const float4& cp, bool finp, const DnSum<VAR>& s) {
     float4 o = cp;
-    if (finp) {  // (a non-finite centre is copied through)
+    float v = dn_var(cp);
+    if (finp) {  // (a non-finite centre is copied through, and keeps its variance)
         o.x = s.r / s.w;
         o.y = s.g / s.w;
         o.z = s.b / s.w;
+        if constexpr (VAR) v = s.v / (s.w * s.w);
     }
-    o.w = finite_f(o.x) && finite_f(o.y) && finite_f(o.z) ? 1.0f : 0.0f;
+    o.w = dn_pack_w<VAR>(v, finite_f(o.x) && finite_f(o.y) && finite_f(o.z));
     return o;
 }
 
 // Steps 1 and 2: a 16x16 tile and its 2 * STEP halo staged in LDS as three float4 planes
 // (20x20 at step 1, 24x24 at step 2: 19 and 27 KB), so each input is fetched once per tile
 // instead of up to 25 times. Cells outside the region are never read (their taps are skipped).
+// The halo (>= 2) covers the pre-blur's +-1.
 constexpr int kDnTile = 16;
-template <int STEP>
+template <bool VAR, int STEP>
 __global__ __launch_bounds__(kDnBlock) void denoise_lds_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                                 const float4* __restrict__ fn,
-                                                                const float4* __restrict__ gp, int w, int h, float k_c) {
+                                                                const float4* __restrict__ gp, int w, int h, float ks) {
     constexpr int R = 2 * STEP, LW = kDnTile + 2 * R;
     __shared__ float4 sc[LW * LW];
     __shared__ float4 sn[LW * LW];
@@ -197,8 +270,10 @@ __global__ __launch_bounds__(kDnBlock) void denoise_lds_kernel(const float4* __r
     if (px >= w || py >= h) return;
     const int lc = (ty + R) * LW + tx + R;
     const float4 cp = sc[lc], np = sn[lc], pp = sp[lc];
-    const bool finp = cp.w != 0.0f, missp = __float_as_int(pp.w) < 0;
-    DnSum s{0.0f, 0.0f, 0.0f, 0.0f};
+    const bool finp = dn_is_finite<VAR>(cp), missp = __float_as_int(pp.w) < 0;
+    DnCentre ce{0.0f, ks};
+    if constexpr (VAR) ce = dn_centre(cp, px, py, w, h, ks, [&](int dx, int dy) { return dn_var(sc[lc + dy * LW + dx]); });
+    DnSum<VAR> s{};
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -206,27 +281,34 @@ __global__ __launch_bounds__(kDnBlock) void denoise_lds_kernel(const float4* __r
             const int qx = px + dx * STEP, qy = py + dy * STEP;
             if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;  // taps outside the region are skipped
             const int lq = lc + dy * STEP * LW + dx * STEP;
-            dn_tap(cp, np, pp, finp, missp, sc[lq], sn[lq], sp[lq], h5(dy + 2) * h5(dx + 2), k_c, s);
+            dn_tap<VAR>(cp, ce, np, pp, finp, missp, sc[lq], sn[lq], sp[lq], h5(dy + 2) * h5(dx + 2), s);
         }
     }
-    dst[(size_t)py * (size_t)w + (size_t)px] = dn_finish(cp, finp, s);
+    dst[(size_t)py * (size_t)w + (size_t)px] = dn_finish<VAR>(cp, finp, s);
 }
 
 // Larger steps: the taps are 4+ pixels apart, so a tile's halo would dwarf it; they read
 // global memory (L2 / MALL). A workgroup is 4 rows of 64 pixels: a wave reads 64 consecutive
-// pixels of a row per tap.
+// pixels of a row per tap. The pre-blur's nine variances are the w lanes of the centre's
+// neighbours, which share its cache lines.
 constexpr int kDnRow = 64;
+template <bool VAR>
 __global__ __launch_bounds__(kDnBlock) void denoise_global_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                                    const float4* __restrict__ fn,
                                                                    const float4* __restrict__ gp, int w, int h, int step,
-                                                                   float k_c) {
+                                                                   float ks) {
     const int px = blockIdx.x * kDnRow + (int)(threadIdx.x & (kDnRow - 1));
     const int py = blockIdx.y * (kDnBlock / kDnRow) + (int)(threadIdx.x / kDnRow);
     if (px >= w || py >= h) return;
     const size_t pc = (size_t)py * (size_t)w + (size_t)px;
     const float4 cp = src[pc], np = fn[pc], pp = gp[pc];
-    const bool finp = cp.w != 0.0f, missp = __float_as_int(pp.w) < 0;
-    DnSum s{0.0f, 0.0f, 0.0f, 0.0f};
+    const bool finp = dn_is_finite<VAR>(cp), missp = __float_as_int(pp.w) < 0;
+    DnCentre ce{0.0f, ks};
+    if constexpr (VAR)
+        ce = dn_centre(cp, px, py, w, h, ks, [&](int dx, int dy) {
+            return dn_var(src[(size_t)(py + dy) * (size_t)w + (size_t)(px + dx)]);
+        });
+    DnSum<VAR> s{};
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
         const int qy = py + dy * step;
@@ -236,14 +318,14 @@ __global__ __launch_bounds__(kDnBlock) void denoise_global_kernel(const float4* 
             const int qx = px + dx * step;
             if (qx < 0 || qx >= w) continue;
             const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
-            dn_tap(cp, np, pp, finp, missp, src[q], fn[q], gp[q], h5(dy + 2) * h5(dx + 2), k_c, s);
+            dn_tap<VAR>(cp, ce, np, pp, finp, missp, src[q], fn[q], gp[q], h5(dy + 2) * h5(dx + 2), s);
         }
     }
-    dst[pc] = dn_finish(cp, finp, s);
+    dst[pc] = dn_finish<VAR>(cp, finp, s);
 }
 
 // ---- launches ---------------------------------------------------------------------------------
-static dim3 grid1(int n) { return dim3((unsigned)std::max(1, (n + kDnBlock - 1) / kDnBlock)); }
+static dim3 grid1(long n) { return dim3((unsigned)std::max(1l, (n + kDnBlock - 1) / kDnBlock)); }
 
 hipError_t launch_guides(const DevScene& S, int trav, const RtRegion& reg, const int32_t* prim_object,
                          const DenoiseGuides& g, int lds_max, hipStream_t stream) {
@@ -284,32 +366,44 @@ hipError_t launch_guides_pack(const DenoiseGuides& g, int n, const float* normal
 }
 
 hipError_t launch_denoise_pack(const float* rad, int pitch_px, int x0, int y0, int w, int h, const float4* gn,
-                               float sigma_plane, float4* colour, float4* fn, hipStream_t stream) {
+                               float sigma_plane, const float* variance, float4* colour, float4* fn,
+                               hipStream_t stream) {
     if (w <= 0 || h <= 0) return hipSuccess;
-    hipLaunchKernelGGL(denoise_pack_kernel, grid1(w * h), dim3(kDnBlock), 0, stream, rad, pitch_px, x0, y0, w, h, gn,
-                       sigma_plane, colour, fn);
+    const auto kernel = variance ? denoise_pack_kernel<true> : denoise_pack_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid1((long)w * h), dim3(kDnBlock), 0, stream, rad, pitch_px, x0, y0, w, h, gn,
+                       sigma_plane, colour, fn, variance);
     return hipGetLastError();
 }
 
-hipError_t launch_denoise_level(const float4* src, float4* dst, const float4* fn, const float4* gp, int w, int h,
-                                int step, float k_c, hipStream_t stream) {
-    if (w <= 0 || h <= 0) return hipSuccess;
+template <bool VAR>
+static void launch_level(const float4* src, float4* dst, const float4* fn, const float4* gp, int w, int h, int step,
+                         float ks, hipStream_t stream) {
     const dim3 tiles((unsigned)((w + kDnTile - 1) / kDnTile), (unsigned)((h + kDnTile - 1) / kDnTile));
     if (step == 1)
-        hipLaunchKernelGGL(denoise_lds_kernel<1>, tiles, dim3(kDnBlock), 0, stream, src, dst, fn, gp, w, h, k_c);
+        hipLaunchKernelGGL((denoise_lds_kernel<VAR, 1>), tiles, dim3(kDnBlock), 0, stream, src, dst, fn, gp, w, h, ks);
     else if (step == 2)
-        hipLaunchKernelGGL(denoise_lds_kernel<2>, tiles, dim3(kDnBlock), 0, stream, src, dst, fn, gp, w, h, k_c);
+        hipLaunchKernelGGL((denoise_lds_kernel<VAR, 2>), tiles, dim3(kDnBlock), 0, stream, src, dst, fn, gp, w, h, ks);
     else
-        hipLaunchKernelGGL(denoise_global_kernel,
+        hipLaunchKernelGGL(denoise_global_kernel<VAR>,
                            dim3((unsigned)((w + kDnRow - 1) / kDnRow),
                                 (unsigned)((h + kDnBlock / kDnRow - 1) / (kDnBlock / kDnRow))),
-                           dim3(kDnBlock), 0, stream, src, dst, fn, gp, w, h, step, k_c);
+                           dim3(kDnBlock), 0, stream, src, dst, fn, gp, w, h, step, ks);
+}
+
+hipError_t launch_denoise_level(bool var, const float4* src, float4* dst, const float4* fn, const float4* gp, int w,
+                                int h, int step, float ks, hipStream_t stream) {
+    if (w <= 0 || h <= 0) return hipSuccess;
+    if (var)
+        launch_level<true>(src, dst, fn, gp, w, h, step, ks, stream);
+    else
+        launch_level<false>(src, dst, fn, gp, w, h, step, ks, stream);
     return hipGetLastError();
 }
 
-hipError_t launch_denoise_unpack(const float4* colour, int n, float* rad, uint8_t* rgb, hipStream_t stream) {
+hipError_t launch_denoise_unpack(const float4* colour, int n, float* rad, uint8_t* rgb, float* variance,
+                                 hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(denoise_unpack_kernel, grid1(n), dim3(kDnBlock), 0, stream, colour, n, rad, rgb);
+    hipLaunchKernelGGL(denoise_unpack_kernel, grid1(n), dim3(kDnBlock), 0, stream, colour, n, rad, rgb, variance);
     return hipGetLastError();
 }
 

@@ -1,11 +1,17 @@
 // First-hit guide buffers and the guided edge-avoiding a-trous filter (rt_camera_render_guides,
-// rt_denoise, rt_camera_denoise, rt_camera_progressive_denoise): denoise.hip. All device arrays
-// here are REGION-PACKED: pixel (i, j) of a w x h region at (x0, y0) is element
-// (j - y0) * w + (i - x0). The filter reads three float4 per pixel:
-//   colour {r, g, b, finite flag (1.0f / 0.0f)}   - ping-pong, one pair per call
+// rt_denoise, rt_camera_denoise, rt_camera_progressive_denoise and their *_variance forms):
+// denoise.hip. All device arrays here are REGION-PACKED: pixel (i, j) of a w x h region at
+// (x0, y0) is element (j - y0) * w + (i - x0). The filter reads three float4 per pixel:
+//   colour {r, g, b, w}                           - ping-pong, one pair per call
 //   fn     {n.xyz, 1 / (sigma_plane * distance)}  - per call (the parameters may change)
 //   gp     {P.xyz, object index bits}             - the guides as the guide pass writes them
 // and the guide pass also keeps gn {n.xyz, distance}, from which fn is made.
+// The filter has two forms, one implementation with a compile-time switch. The plain form
+// stops at colour edges by the RGB distance over a launch-wide sigma_color, and colour.w is the
+// pixel's finite flag (1.0f / 0.0f). The variance-guided form stops by the luminance difference
+// relative to the centre pixel's own (3x3 pre-blurred) variance and filters the variance along
+// with the colour: colour.w is the variance, >= 0 as a value, and its SIGN BIT is the pixel's
+// "colour is not finite" flag.
 // No reference counterpart: the reference renders a frame and never filters it.
 #pragma once
 
@@ -36,16 +42,22 @@ hipError_t launch_guides_unpack(const DenoiseGuides& g, int n, float* normal, fl
 hipError_t launch_guides_pack(const DenoiseGuides& g, int n, const float* normal, const float* position,
                               const float* distance, const int32_t* object, hipStream_t stream);
 
-// The filter's per-call inputs: colour {r, g, b, finite} from `rad` (float[3] per pixel, row
-// pitch `pitch_px` pixels, the region's first pixel at rad + 3 * (y0 * pitch_px + x0)), and
-// fn = {n.xyz, 1 / (sigma_plane * distance)} from gn.
+// The filter's per-call inputs: colour from `rad` (float[3] per pixel, row pitch `pitch_px`
+// pixels, the region's first pixel at rad + 3 * (y0 * pitch_px + x0)), and
+// fn = {n.xyz, 1 / (sigma_plane * distance)} from gn. `variance` (region-packed; not (v >= 0 and
+// finite) -> 0) selects the variance-guided form's colour.w, null the plain one's.
 hipError_t launch_denoise_pack(const float* rad, int pitch_px, int x0, int y0, int w, int h, const float4* gn,
-                               float sigma_plane, float4* colour, float4* fn, hipStream_t stream);
-// One level: step = 1 << level taps of the 5x5 B3 kernel, k_c = 4^level / sigma_color^2 (host).
+                               float sigma_plane, const float* variance, float4* colour, float4* fn,
+                               hipStream_t stream);
+// One level: step = 1 << level taps of the 5x5 B3 kernel. ks (host, double -> fp32): the plain
+// form's k_c = 4^level / sigma_color^2, or with `var` the variance-guided form's
+// s2 = sigma_variance^2, whose 3x3 variance pre-blur of the centre pixel runs inside the kernel.
 // Steps 1 and 2 stage a 16x16 tile plus halo in LDS; larger steps read global memory.
-hipError_t launch_denoise_level(const float4* src, float4* dst, const float4* fn, const float4* gp, int w, int h,
-                                int step, float k_c, hipStream_t stream);
-// colour -> region-packed float[3] radiance and / or its u8 (the frame's own to_u8).
-hipError_t launch_denoise_unpack(const float4* colour, int n, float* rad, uint8_t* rgb, hipStream_t stream);
+hipError_t launch_denoise_level(bool var, const float4* src, float4* dst, const float4* fn, const float4* gp, int w,
+                                int h, int step, float ks, hipStream_t stream);
+// colour -> region-packed float[3] radiance and / or its u8 (the frame's own to_u8) and / or,
+// after the variance-guided form, the filtered variance (the flag bit cleared).
+hipError_t launch_denoise_unpack(const float4* colour, int n, float* rad, uint8_t* rgb, float* variance,
+                                 hipStream_t stream);
 
 }  // namespace rt

@@ -165,6 +165,29 @@ __global__ __launch_bounds__(kProgBlock) void pt_resolve_kernel(DevScene S0, RtR
     }
 }
 
+// State -> the variance map (prog_variance of every pixel of the region).
+__global__ __launch_bounds__(kProgBlock) void prog_variance_kernel(const ProgPix* __restrict__ state, int slots,
+                                                                    RtRegion reg, int tiles_x,
+                                                                    float* __restrict__ variance) {
+    const int slot = blockIdx.x * kProgBlock + (int)threadIdx.x;
+    if (slot >= slots) return;
+    int i, j;
+    item_pixel(reg, tiles_x, slot / kWave, slot & (kWave - 1), i, j);
+    if (i >= reg.x + reg.width || j >= reg.y + reg.height) return;
+    const uint32_t n = __float_as_uint(state[slot].c.w) & ~kProgFinished;
+    const double2 ill = state[slot].ill;
+    variance[(size_t)(j - reg.y) * (size_t)reg.width + (size_t)(i - reg.x)] = prog_variance(ill.x, ill.y, n);
+}
+
+hipError_t launch_prog_variance(const ProgPix* state, int slots, const RtRegion& reg, int tiles_x, float* variance,
+                                hipStream_t stream) {
+    if (slots <= 0) return hipSuccess;
+    const RtRegion r{reg.x, reg.y, reg.width, reg.height, 0, 1};
+    hipLaunchKernelGGL(prog_variance_kernel, dim3((unsigned)((slots + kProgBlock - 1) / kProgBlock)), dim3(kProgBlock), 0,
+                       stream, state, slots, r, tiles_x, variance);
+    return hipGetLastError();
+}
+
 hipError_t launch_settle(const DevScene& S, const RtRegion& reg, const RenderOut& out, int tiles_x,
                          const SampleBuf& sb, const ProgPass& pp, hipStream_t stream) {
     const int grid = std::max(1, std::min((sb.slots + kProgBlock - 1) / kProgBlock, 1024));

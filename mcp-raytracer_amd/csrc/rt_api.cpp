@@ -27,7 +27,6 @@
 
 #include "../../include/rt_amd.h"
 #include "denoise.hpp"
-#include "denoise_var.hpp"
 #include "json.hpp"
 #include "launch.hpp"
 #include "progressive.hpp"
@@ -146,7 +145,7 @@ struct DnBufs {
     int32_t* obj = nullptr;
     uint8_t* u8 = nullptr;
     size_t cap = 0;  // pixels
-    float* var = nullptr;  // region-packed variance of the variance-guided calls (denoise_var.hpp)
+    float* var = nullptr;  // region-packed variance of the variance-guided calls
     size_t var_cap = 0;
     float* rad() const { return stage; }
     float* nrm() const { return stage + 3 * cap; }
@@ -183,24 +182,32 @@ struct DnBufs {
     }
 };
 
-// rt_denoise_options resolved: NULL or a zero field = the default.
+// The fields of rt_denoise_options / rt_denoise_var_options (NULL: all zero) as the caller gave
+// them, then resolved by dn_resolve: a zero field = the default. var: the variance-guided
+// filter, whose sigma is sigma_variance (the plain one's: sigma_color).
 struct DnOpts {
-    int32_t levels = 4;
-    float sigma_color = 0.5f, sigma_plane = 0.01f;
+    bool var;
+    int32_t levels;
+    float sigma, sigma_plane;
 };
-static DnOpts dn_options(const rt_denoise_options* o, const std::string& who) {
-    DnOpts r;
-    if (!o) return r;
-    if (o->levels < 0 || o->levels > kDenoiseMaxLevels)
+static DnOpts dn_options(const rt_denoise_options* o) {
+    return o ? DnOpts{false, o->levels, o->sigma_color, o->sigma_plane} : DnOpts{false, 0, 0.0f, 0.0f};
+}
+static DnOpts dn_options(const rt_denoise_var_options* o) {
+    return o ? DnOpts{true, o->levels, o->sigma_variance, o->sigma_plane} : DnOpts{true, 0, 0.0f, 0.0f};
+}
+static DnOpts dn_resolve(DnOpts o, const std::string& who) {
+    if (o.levels < 0 || o.levels > kDenoiseMaxLevels)
         throw std::invalid_argument(who + ": levels must be 1.." + std::to_string(kDenoiseMaxLevels) + " (0: the default)");
-    if (!(o->sigma_color >= 0.0f) || !std::isfinite(o->sigma_color))
-        throw std::invalid_argument(who + ": sigma_color must be positive and finite (0: the default)");
-    if (!(o->sigma_plane >= 0.0f) || !std::isfinite(o->sigma_plane))
+    if (!(o.sigma >= 0.0f) || !std::isfinite(o.sigma))
+        throw std::invalid_argument(who + (o.var ? ": sigma_variance" : ": sigma_color") +
+                                    " must be positive and finite (0: the default)");
+    if (!(o.sigma_plane >= 0.0f) || !std::isfinite(o.sigma_plane))
         throw std::invalid_argument(who + ": sigma_plane must be positive and finite (0: the default)");
-    if (o->levels) r.levels = o->levels;
-    if (o->sigma_color != 0.0f) r.sigma_color = o->sigma_color;
-    if (o->sigma_plane != 0.0f) r.sigma_plane = o->sigma_plane;
-    return r;
+    if (!o.levels) o.levels = 4;
+    if (o.sigma == 0.0f) o.sigma = o.var ? 2.0f : 0.5f;
+    if (o.sigma_plane == 0.0f) o.sigma_plane = 0.01f;
+    return o;
 }
 
 // `region` (NULL: the whole image) clamped to a width x height image; empty: an argument error.
@@ -231,76 +238,35 @@ static void dn_download(void* host, const void* dev, size_t elem, int32_t width,
 }
 
 // The filter over a w x h region whose guides are gn / gp: colour and fn from `rad` (row pitch
-// `pitch_px` pixels, region at (x0, y0)), one launch per level over the ping-pong pair, then
-// the result into b.rad() / b.u8 (region-packed). ev (or null): levels + 3 events, recorded
-// before the pack pass, after it, after every level and after the unpack pass. Queued.
+// `pitch_px` pixels, region at (x0, y0)) and, variance-guided, from the region-packed b.var; one
+// launch per level over the ping-pong pair, then the result into b.rad() / b.u8 and, when
+// want_var, the filtered variance into b.var (region-packed). ev (or null): levels + 3 events,
+// recorded before the pack pass, after it, after every level and after the unpack pass. Queued.
 static void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0,
-                      int w, int h, const DnOpts& o, bool want_rad, bool want_u8, hipStream_t stream, hipEvent_t* ev) {
+                      int w, int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream,
+                      hipEvent_t* ev) {
     int e = 0;
     auto mark = [&] {
         if (ev) hip_check(hipEventRecord(ev[e++], stream), "hipEventRecord");
     };
     mark();
-    hip_check(launch_denoise_pack(rad, pitch_px, x0, y0, w, h, gn, o.sigma_plane, b.c0, b.fn, stream), "denoise_pack_kernel");
+    hip_check(launch_denoise_pack(rad, pitch_px, x0, y0, w, h, gn, o.sigma_plane, o.var ? b.var : nullptr, b.c0, b.fn,
+                                  stream),
+              "denoise_pack_kernel");
     mark();
+    // the level's scalar, in double on the host, rounded to fp32 once: sigma_variance^2, or
+    // 4^level / sigma_color^2
+    const double s2 = (double)o.sigma * (double)o.sigma;
     float4 *src = b.c0, *dst = b.c1;
     for (int lv = 0; lv < o.levels; ++lv) {
-        // 4^level / sigma_color^2: in double on the host, rounded to fp32 once
-        const float k_c = (float)(std::ldexp(1.0, 2 * lv) / ((double)o.sigma_color * (double)o.sigma_color));
-        hip_check(launch_denoise_level(src, dst, b.fn, gp, w, h, 1 << lv, k_c, stream), "denoise kernel");
+        const float ks = (float)(o.var ? s2 : std::ldexp(1.0, 2 * lv) / s2);
+        hip_check(launch_denoise_level(o.var, src, dst, b.fn, gp, w, h, 1 << lv, ks, stream), "denoise kernel");
         mark();
         std::swap(src, dst);
     }
-    hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8 : nullptr, stream),
+    hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8 : nullptr,
+                                    o.var && want_var ? b.var : nullptr, stream),
               "denoise_unpack_kernel");
-    mark();
-}
-
-// rt_denoise_var_options resolved: NULL or a zero field = the default.
-struct DnvOpts {
-    int32_t levels = 4;
-    float sigma_variance = 2.0f, sigma_plane = 0.01f;
-};
-static DnvOpts dnv_options(const rt_denoise_var_options* o, const std::string& who) {
-    DnvOpts r;
-    if (!o) return r;
-    if (o->levels < 0 || o->levels > kDenoiseMaxLevels)
-        throw std::invalid_argument(who + ": levels must be 1.." + std::to_string(kDenoiseMaxLevels) + " (0: the default)");
-    if (!(o->sigma_variance >= 0.0f) || !std::isfinite(o->sigma_variance))
-        throw std::invalid_argument(who + ": sigma_variance must be positive and finite (0: the default)");
-    if (!(o->sigma_plane >= 0.0f) || !std::isfinite(o->sigma_plane))
-        throw std::invalid_argument(who + ": sigma_plane must be positive and finite (0: the default)");
-    if (o->levels) r.levels = o->levels;
-    if (o->sigma_variance != 0.0f) r.sigma_variance = o->sigma_variance;
-    if (o->sigma_plane != 0.0f) r.sigma_plane = o->sigma_plane;
-    return r;
-}
-
-// The variance-guided filter (denoise_var.hpp), as dn_filter: the colour's w carries the
-// region-packed variance b.var, which receives the filtered variance when want_var. Events as
-// dn_filter's (the variance unpack falls into the last span). Queued.
-static void dnv_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0,
-                       int w, int h, const DnvOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream,
-                       hipEvent_t* ev) {
-    int e = 0;
-    auto mark = [&] {
-        if (ev) hip_check(hipEventRecord(ev[e++], stream), "hipEventRecord");
-    };
-    mark();
-    hip_check(launch_denoise_var_pack(rad, pitch_px, x0, y0, w, h, gn, o.sigma_plane, b.var, b.c0, b.fn, stream),
-              "denoise_var_pack_kernel");
-    mark();
-    // sigma_variance^2: in double on the host, rounded to fp32 once
-    const float s2 = (float)((double)o.sigma_variance * (double)o.sigma_variance);
-    float4 *src = b.c0, *dst = b.c1;
-    for (int lv = 0; lv < o.levels; ++lv) {
-        hip_check(launch_denoise_var_level(src, dst, b.fn, gp, w, h, 1 << lv, s2, stream), "denoise_var kernel");
-        mark();
-        std::swap(src, dst);
-    }
-    hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8 : nullptr, stream),
-              "denoise_unpack_kernel");
-    if (want_var) hip_check(launch_denoise_var_unpack(src, w * h, b.var, stream), "denoise_var_unpack_kernel");
     mark();
 }
 
@@ -2430,21 +2396,32 @@ int rt_camera_render_guides(rt_camera* cam, const rt_region* region, float* norm
     });
 }
 
-int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,
-               const float* radiance, const float* normal, const float* position, const float* distance,
-               const int32_t* object, float* radiance_out, uint8_t* rgb_out) {
+// The three shapes of a filter call, plain or variance-guided (o.var: `variance` in, or the
+// session's own, and `variance_out`); `o` as dn_options gives it, resolved where the entry point
+// always has. Every argument error comes before anything touches a device.
+
+// The stand-alone frame call: explicit guides, buffers of its own.
+static int dn_frame_call(const std::string& who, DnOpts o, int32_t width, int32_t height, const rt_region* region,
+                         const float* radiance, const float* variance, const float* normal, const float* position,
+                         const float* distance, const int32_t* object, float* radiance_out, float* variance_out,
+                         uint8_t* rgb_out) {
     DnBufs b;
     int rc = RT_OK;
     try {
-        if (width <= 0 || height <= 0) throw std::invalid_argument("rt_denoise: width and height must be positive");
-        if (!radiance || !normal || !position || !distance || !object)
-            throw std::invalid_argument("rt_denoise: radiance, normal, position, distance and object are required");
-        const DnOpts o = dn_options(options, "rt_denoise");
-        const rt_region r = dn_region(region, width, height, "rt_denoise");
+        if (width <= 0 || height <= 0) throw std::invalid_argument(who + ": width and height must be positive");
+        if (!radiance || (o.var && !variance) || !normal || !position || !distance || !object)
+            throw std::invalid_argument(who + ": radiance, " + (o.var ? "variance, " : "") +
+                                        "normal, position, distance and object are required");
+        o = dn_resolve(o, who);
+        const rt_region r = dn_region(region, width, height, who);
         const hipStream_t stream = nullptr;
         const int n = r.width * r.height;
         b.ensure((size_t)n);
         dn_upload(b.rad(), radiance, 3 * sizeof(float), width, r, stream);
+        if (o.var) {
+            b.ensure_var((size_t)n);
+            dn_upload(b.var, variance, sizeof(float), width, r, stream);
+        }
         dn_upload(b.nrm(), normal, 3 * sizeof(float), width, r, stream);
         dn_upload(b.pos(), position, 3 * sizeof(float), width, r, stream);
         dn_upload(b.dist(), distance, sizeof(float), width, r, stream);
@@ -2452,8 +2429,9 @@ int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_
         const DenoiseGuides g{b.gn, b.gp};
         hip_check(launch_guides_pack(g, n, b.nrm(), b.pos(), b.dist(), b.obj, stream), "guides_pack_kernel");
         dn_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
-                  rgb_out != nullptr, stream, nullptr);
+                  rgb_out != nullptr, variance_out != nullptr, stream, nullptr);
         dn_download(radiance_out, b.rad(), 3 * sizeof(float), width, r, stream);
+        if (o.var) dn_download(variance_out, b.var, sizeof(float), width, r, stream);
         dn_download(rgb_out, b.u8, 3, width, r, stream);
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     } catch (const HipError& e) {
@@ -2467,13 +2445,16 @@ int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_
     return rc;
 }
 
-int rt_camera_denoise(rt_camera* cam, const rt_region* region, const rt_denoise_options* options, const float* radiance,
-                      float* radiance_out, uint8_t* rgb_out) {
+// The camera call: the guide pass of the camera's scene over the region, the camera's buffers.
+static int dn_camera_call(rt_camera* cam, const std::string& who, DnOpts o, const rt_region* region,
+                          const float* radiance, const float* variance, float* radiance_out, float* variance_out,
+                          uint8_t* rgb_out) {
     return camera_call(cam, [&] {
         const RtCamera& C = cam->build.cam;
-        if (!radiance) throw std::invalid_argument("rt_camera_denoise: radiance is required");
-        const DnOpts o = dn_options(options, "rt_camera_denoise");
-        const rt_region r = dn_region(region, C.width, C.height, "rt_camera_denoise");
+        if (!radiance || (o.var && !variance))
+            throw std::invalid_argument(who + (o.var ? ": radiance and variance are required" : ": radiance is required"));
+        o = dn_resolve(o, who);
+        const rt_region r = dn_region(region, C.width, C.height, who);
         DevCtx& c = cam->current();
         c.ensure_device();
         const hipStream_t stream = nullptr;
@@ -2481,72 +2462,57 @@ int rt_camera_denoise(rt_camera* cam, const rt_region* region, const rt_denoise_
         b.ensure((size_t)r.width * r.height);
         hipEvent_t* ev = c.dn_events(o.levels);
         dn_upload(b.rad(), radiance, 3 * sizeof(float), C.width, r, stream);
+        if (o.var) {
+            b.ensure_var((size_t)r.width * r.height);
+            dn_upload(b.var, variance, sizeof(float), C.width, r, stream);
+        }
         hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
         c.launch_guide_pass(r, cam->traversal, DenoiseGuides{b.gn, b.gp}, stream);
         c.dn_guides = true;
         dn_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
-                  rgb_out != nullptr, stream, ev + 1);
+                  rgb_out != nullptr, variance_out != nullptr, stream, ev + 1);
         dn_download(radiance_out, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        if (o.var) dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
         dn_download(rgb_out, b.u8, 3, C.width, r, stream);
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     });
 }
 
-int rt_camera_progressive_denoise(rt_camera* cam, const rt_denoise_options* options, uint8_t* rgb, float* radiance) {
-    return camera_call(cam, [&] {
-        DevCtx& c = cam->session("rt_camera_progressive_denoise");
-        const RtCamera& C = cam->build.cam;
-        if (C.mode != MODE_DEFAULT)
-            throw std::invalid_argument("rt_camera_progressive_denoise: the frames of mode bounces / samples are not radiance");
-        const DnOpts o = dn_options(options, "rt_camera_progressive_denoise");
-        int dev = 0;
-        hip_check(hipGetDevice(&dev), "hipGetDevice");
-        if (dev != c.device)
-            throw std::invalid_argument("rt_camera_progressive_denoise: the session lives on another device");
-        DevCtx::ProgSession& P = c.prog;
-        const rt_region r = P.region;
-        const hipStream_t stream = nullptr;
-        const size_t n = (size_t)r.width * r.height;
-        DnBufs& b = c.dn;
-        b.ensure(n);
-        hipEvent_t* ev = c.dn_events(o.levels);
-        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
-        c.dn_guides = !P.d_gn;
-        if (!P.d_gn) {  // the region's guides: computed once, freed with the session
-            try {
-                hip_check(hipMalloc(&P.d_gn, n * sizeof(float4)), "hipMalloc(session guides)");
-                hip_check(hipMalloc(&P.d_gp, n * sizeof(float4)), "hipMalloc(session guides)");
-                c.launch_guide_pass(r, cam->traversal, DenoiseGuides{P.d_gn, P.d_gp}, stream);
-            } catch (...) {
-                if (P.d_gn) (void)hipFree(P.d_gn);
-                if (P.d_gp) (void)hipFree(P.d_gp);
-                P.d_gn = P.d_gp = nullptr;
-                throw;
-            }
-        }
-        // the session's device frame as it stands after the last step: nothing is uploaded
-        dn_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, r.x, r.y, r.width, r.height, o, radiance != nullptr, rgb != nullptr,
-                  stream, ev + 1);
-        dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
-        dn_download(rgb, b.u8, 3, C.width, r, stream);
-        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    });
-}
-
-// ---- Variance map and the variance-guided filter (denoise_var.hpp) -----------------------------
-// The open session whose state holds a variance: mode default and two samples or more. Argument
-// errors first, then the device check.
-static DevCtx& variance_session(rt_camera* cam, const std::string& who) {
-    DevCtx& c = cam->session(who.c_str());
+// The open session's frames must be radiance.
+static void session_radiance(rt_camera* cam, const std::string& who) {
     if (cam->build.cam.mode != MODE_DEFAULT)
         throw std::invalid_argument(who + ": the frames of mode bounces / samples are not radiance");
-    if (c.prog.done < 2)
+}
+
+// The open session, on the current device, whose state holds radiance and at least min_samples
+// samples per pixel (2: a variance). Argument errors first, then the device check.
+static DevCtx& session_with(rt_camera* cam, const std::string& who, int min_samples) {
+    DevCtx& c = cam->session(who.c_str());
+    session_radiance(cam, who);
+    if (c.prog.done < min_samples)
         throw std::invalid_argument(who + ": a variance needs at least 2 samples per pixel, the session has " +
                                     std::to_string(c.prog.done) + " (samples_done < 2)");
     int dev = 0;
     hip_check(hipGetDevice(&dev), "hipGetDevice");
     if (dev != c.device) throw std::invalid_argument(who + ": the session lives on another device");
     return c;
+}
+
+// The session's guides: computed once (queued), freed with the session.
+static void session_guides(rt_camera* cam, DevCtx& c, hipStream_t stream) {
+    DevCtx::ProgSession& P = c.prog;
+    if (P.d_gn) return;
+    const size_t n = (size_t)P.region.width * P.region.height;
+    try {
+        hip_check(hipMalloc(&P.d_gn, n * sizeof(float4)), "hipMalloc(session guides)");
+        hip_check(hipMalloc(&P.d_gp, n * sizeof(float4)), "hipMalloc(session guides)");
+        c.launch_guide_pass(P.region, cam->traversal, DenoiseGuides{P.d_gn, P.d_gp}, stream);
+    } catch (...) {
+        if (P.d_gn) (void)hipFree(P.d_gn);
+        if (P.d_gp) (void)hipFree(P.d_gp);
+        P.d_gn = P.d_gp = nullptr;
+        throw;
+    }
 }
 
 // The session's state -> b.var (region-packed); queued.
@@ -2558,127 +2524,83 @@ static void prog_variance_pass(DevCtx& c, hipStream_t stream) {
               "prog_variance_kernel");
 }
 
-int rt_camera_progressive_variance(rt_camera* cam, float* variance) {
+// The session call: the session's device frame (and, variance-guided, its state) as they stand
+// after the last step - nothing is uploaded - and the session's guides.
+static int dn_session_call(rt_camera* cam, const std::string& who, DnOpts o, uint8_t* rgb, float* radiance,
+                           float* variance_out) {
     return camera_call(cam, [&] {
-        if (!variance) throw std::invalid_argument("rt_camera_progressive_variance: variance is required");
-        DevCtx& c = variance_session(cam, "rt_camera_progressive_variance");
+        (void)cam->session(who.c_str());
+        // (the plain call names a wrong mode before its options, the variance-guided one its
+        // options before the mode and the sample count)
+        if (!o.var) session_radiance(cam, who);
+        o = dn_resolve(o, who);
+        DevCtx& c = session_with(cam, who, o.var ? 2 : 0);
+        const RtCamera& C = cam->build.cam;
+        DevCtx::ProgSession& P = c.prog;
+        const rt_region r = P.region;
         const hipStream_t stream = nullptr;
-        prog_variance_pass(c, stream);
-        dn_download(variance, c.dn.var, sizeof(float), cam->build.cam.width, c.prog.region, stream);
+        DnBufs& b = c.dn;
+        b.ensure((size_t)r.width * r.height);
+        hipEvent_t* ev = c.dn_events(o.levels);
+        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+        // the span [0, 1): the guide pass of a first call and, variance-guided, the variance pass
+        c.dn_guides = o.var || !P.d_gn;
+        session_guides(cam, c, stream);
+        if (o.var) prog_variance_pass(c, stream);
+        dn_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, r.x, r.y, r.width, r.height, o, radiance != nullptr, rgb != nullptr,
+                  variance_out != nullptr, stream, ev + 1);
+        dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        if (o.var) dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
+        dn_download(rgb, b.u8, 3, C.width, r, stream);
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     });
+}
+
+int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,
+               const float* radiance, const float* normal, const float* position, const float* distance,
+               const int32_t* object, float* radiance_out, uint8_t* rgb_out) {
+    return dn_frame_call("rt_denoise", dn_options(options), width, height, region, radiance, nullptr, normal, position,
+                         distance, object, radiance_out, nullptr, rgb_out);
 }
 
 int rt_denoise_variance(int32_t width, int32_t height, const rt_region* region, const rt_denoise_var_options* options,
                         const float* radiance, const float* variance, const float* normal, const float* position,
                         const float* distance, const int32_t* object, float* radiance_out, float* variance_out,
                         uint8_t* rgb_out) {
-    DnBufs b;
-    int rc = RT_OK;
-    try {
-        if (width <= 0 || height <= 0) throw std::invalid_argument("rt_denoise_variance: width and height must be positive");
-        if (!radiance || !variance || !normal || !position || !distance || !object)
-            throw std::invalid_argument(
-                "rt_denoise_variance: radiance, variance, normal, position, distance and object are required");
-        const DnvOpts o = dnv_options(options, "rt_denoise_variance");
-        const rt_region r = dn_region(region, width, height, "rt_denoise_variance");
-        const hipStream_t stream = nullptr;
-        const int n = r.width * r.height;
-        b.ensure((size_t)n);
-        b.ensure_var((size_t)n);
-        dn_upload(b.rad(), radiance, 3 * sizeof(float), width, r, stream);
-        dn_upload(b.var, variance, sizeof(float), width, r, stream);
-        dn_upload(b.nrm(), normal, 3 * sizeof(float), width, r, stream);
-        dn_upload(b.pos(), position, 3 * sizeof(float), width, r, stream);
-        dn_upload(b.dist(), distance, sizeof(float), width, r, stream);
-        dn_upload(b.obj, object, sizeof(int32_t), width, r, stream);
-        const DenoiseGuides g{b.gn, b.gp};
-        hip_check(launch_guides_pack(g, n, b.nrm(), b.pos(), b.dist(), b.obj, stream), "guides_pack_kernel");
-        dnv_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
-                   rgb_out != nullptr, variance_out != nullptr, stream, nullptr);
-        dn_download(radiance_out, b.rad(), 3 * sizeof(float), width, r, stream);
-        dn_download(variance_out, b.var, sizeof(float), width, r, stream);
-        dn_download(rgb_out, b.u8, 3, width, r, stream);
-        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    } catch (const HipError& e) {
-        rc = set_error(RT_ERR_DEVICE, e.what());
-    } catch (const std::invalid_argument& e) {
-        rc = set_error(RT_ERR_INVALID, e.what());
-    } catch (const std::exception& e) {
-        rc = set_error(RT_ERR_RENDER, e.what());
-    }
-    b.free();
-    return rc;
+    return dn_frame_call("rt_denoise_variance", dn_options(options), width, height, region, radiance, variance, normal,
+                         position, distance, object, radiance_out, variance_out, rgb_out);
+}
+
+int rt_camera_denoise(rt_camera* cam, const rt_region* region, const rt_denoise_options* options, const float* radiance,
+                      float* radiance_out, uint8_t* rgb_out) {
+    return dn_camera_call(cam, "rt_camera_denoise", dn_options(options), region, radiance, nullptr, radiance_out, nullptr,
+                          rgb_out);
 }
 
 int rt_camera_denoise_variance(rt_camera* cam, const rt_region* region, const rt_denoise_var_options* options,
                                const float* radiance, const float* variance, float* radiance_out, float* variance_out,
                                uint8_t* rgb_out) {
-    return camera_call(cam, [&] {
-        const RtCamera& C = cam->build.cam;
-        if (!radiance || !variance)
-            throw std::invalid_argument("rt_camera_denoise_variance: radiance and variance are required");
-        const DnvOpts o = dnv_options(options, "rt_camera_denoise_variance");
-        const rt_region r = dn_region(region, C.width, C.height, "rt_camera_denoise_variance");
-        DevCtx& c = cam->current();
-        c.ensure_device();
-        const hipStream_t stream = nullptr;
-        DnBufs& b = c.dn;
-        b.ensure((size_t)r.width * r.height);
-        b.ensure_var((size_t)r.width * r.height);
-        hipEvent_t* ev = c.dn_events(o.levels);
-        dn_upload(b.rad(), radiance, 3 * sizeof(float), C.width, r, stream);
-        dn_upload(b.var, variance, sizeof(float), C.width, r, stream);
-        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
-        c.launch_guide_pass(r, cam->traversal, DenoiseGuides{b.gn, b.gp}, stream);
-        c.dn_guides = true;
-        dnv_filter(b, b.gn, b.gp, b.rad(), r.width, 0, 0, r.width, r.height, o, radiance_out != nullptr,
-                   rgb_out != nullptr, variance_out != nullptr, stream, ev + 1);
-        dn_download(radiance_out, b.rad(), 3 * sizeof(float), C.width, r, stream);
-        dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
-        dn_download(rgb_out, b.u8, 3, C.width, r, stream);
-        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    });
+    return dn_camera_call(cam, "rt_camera_denoise_variance", dn_options(options), region, radiance, variance,
+                          radiance_out, variance_out, rgb_out);
+}
+
+int rt_camera_progressive_denoise(rt_camera* cam, const rt_denoise_options* options, uint8_t* rgb, float* radiance) {
+    return dn_session_call(cam, "rt_camera_progressive_denoise", dn_options(options), rgb, radiance, nullptr);
 }
 
 int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_options* options, uint8_t* rgb,
                                            float* radiance, float* variance_out) {
+    return dn_session_call(cam, "rt_camera_progressive_denoise_variance", dn_options(options), rgb, radiance,
+                           variance_out);
+}
+
+int rt_camera_progressive_variance(rt_camera* cam, float* variance) {
     return camera_call(cam, [&] {
-        const std::string who = "rt_camera_progressive_denoise_variance";
-        const RtCamera& C = cam->build.cam;
-        // (the options before the session's sample count: every argument error needs no device)
-        (void)cam->session(who.c_str());
-        const DnvOpts o = dnv_options(options, who);
-        DevCtx& c = variance_session(cam, who);
-        DevCtx::ProgSession& P = c.prog;
-        const rt_region r = P.region;
+        if (!variance) throw std::invalid_argument("rt_camera_progressive_variance: variance is required");
+        DevCtx& c = session_with(cam, "rt_camera_progressive_variance", 2);
         const hipStream_t stream = nullptr;
-        const size_t n = (size_t)r.width * r.height;
-        DnBufs& b = c.dn;
-        b.ensure(n);
-        b.ensure_var(n);
-        hipEvent_t* ev = c.dn_events(o.levels);
-        hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
-        c.dn_guides = true;  // the span [0, 1): the variance pass, after the guide pass of a first call
-        if (!P.d_gn) {  // the region's guides: computed once, freed with the session
-            try {
-                hip_check(hipMalloc(&P.d_gn, n * sizeof(float4)), "hipMalloc(session guides)");
-                hip_check(hipMalloc(&P.d_gp, n * sizeof(float4)), "hipMalloc(session guides)");
-                c.launch_guide_pass(r, cam->traversal, DenoiseGuides{P.d_gn, P.d_gp}, stream);
-            } catch (...) {
-                if (P.d_gn) (void)hipFree(P.d_gn);
-                if (P.d_gp) (void)hipFree(P.d_gp);
-                P.d_gn = P.d_gp = nullptr;
-                throw;
-            }
-        }
         prog_variance_pass(c, stream);
-        // the session's device frame and state as they stand after the last step: nothing is uploaded
-        dnv_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, r.x, r.y, r.width, r.height, o, radiance != nullptr, rgb != nullptr,
-                   variance_out != nullptr, stream, ev + 1);
-        dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
-        dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
-        dn_download(rgb, b.u8, 3, C.width, r, stream);
+        dn_download(variance, c.dn.var, sizeof(float), cam->build.cam.width, c.prog.region, stream);
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     });
 }

@@ -47,12 +47,10 @@ _UNITS = [
     ("pt_ref.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     ("pt_fp32.hip", ["-ffp-contract=fast", *_KERNEL_FLAGS], True),
     ("progressive.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
-    # guide pass + a-trous filter: every fp32 operation must round once (no contraction; plain /
-    # and sqrtf are IEEE under hipcc's defaults) - the output equals tests/denoise_ref.py in every bit
+    # guide pass + a-trous filter, plain and variance-guided: every fp32 operation must round once
+    # (no contraction; plain / and sqrtf are IEEE under hipcc's defaults) - the output equals
+    # tests/denoise_ref.py and tests/denoise_var_ref.py in every bit
     ("denoise.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
-    # variance map + variance-guided filter: as denoise.hip (tests/denoise_var_ref.py); the fp64
-    # variance formula is also evaluated on the host in rt_api.cpp, which never contracts either
-    ("denoise_var.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     ("frame.hip", [], True),
     ("png.hip", [], True),
     ("rt_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
@@ -60,7 +58,6 @@ _UNITS = [
     ("image.cpp", [], False),
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "denoise_var.hpp",
             "png_deflate.hpp"]
 _LIBS = ["-lz"]
 

@@ -171,10 +171,9 @@ def test_filter_of_a_region(rt, cornell40):
                                  "cornell40 region", region=REGION)
 
 
-def synthetic_frame():
+def synthetic_frame(H=23, W=37):
     f = np.float32
     rng = np.random.default_rng(11)
-    H, W = 23, 37
     s = f(1) / np.sqrt(f(3))
     dirs = np.array([[a, b, c] for a in (-s, s) for b in (-s, s) for c in (-s, s)], dtype=f)  # 8 unit directions
     n = dirs[rng.integers(0, 8, (H, W))]
@@ -211,6 +210,15 @@ def test_filter_of_a_synthetic_frame_with_non_finite_pixels(rt, gpu):
     assert int(bad.sum()) == 2 and bad[5, 7] and bad[12, 30] and out[20, 3, 2] == np.float32(1e30)
     assert vout[5, 7] == np.float32(7.5) and vout[12, 30] == var[12, 30]
     assert np.isfinite(vout).all() and (vout >= 0).all()
+
+
+def test_filter_of_a_synthetic_frame_wider_than_a_row_group(rt, gpu):
+    """70x21: the global kernel (step 4) covers 64 pixels of 4 rows per workgroup, so 70 crosses
+    its row group and the 16-pixel tiles with a ragged edge, 21 its 4 rows and a tile. The
+    variance map is compared with the colour."""
+    c, var, n, P, dist, obj = synthetic_frame(21, 70)
+    assert_filter_is_restatement(rt, c, var, n, P, dist, obj, "synthetic 70x21", levels=3, sigma_variance=0.7,
+                                 sigma_plane=0.05)
 
 
 # ---- 3. the entries ------------------------------------------------------------------------------
