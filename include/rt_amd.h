@@ -38,7 +38,8 @@ enum {
     RT_OK = 0,
     RT_ERR_INVALID = 1,   /* bad arguments / scene (reference throws an Error) */
     RT_ERR_DEVICE = 2,    /* HIP error */
-    RT_ERR_RENDER = 3     /* error raised during rendering (e.g. miss without background) */
+    RT_ERR_RENDER = 3,    /* error raised during rendering (e.g. miss without background) */
+    RT_PRIMARY_TABLE_NONE = 4  /* rt_camera_primary_table: the camera has no primary-ray table */
 };
 
 enum { RT_PRECISION_REF = 0, RT_PRECISION_FP32 = 1 };
@@ -221,6 +222,39 @@ int rt_camera_pass_count(rt_camera* cam, int32_t* passes);
  * in round 4; they are not reused.) */
 enum { RT_KERNEL_NONE = 0, RT_KERNEL_SEQUENTIAL = 1, RT_KERNEL_CHUNKED = 2, RT_KERNEL_POOL = 3 };
 int rt_camera_last_kernel(rt_camera* cam, int32_t* kernel);
+
+/* The primary-ray candidate table of the pool kernel. With a pinhole camera (aperture 0)
+ * every primary ray of a pixel starts at the camera centre and points into the pixel's
+ * footprint, so which of the scene's <= 16 brute-force primitives such a ray can hit, and
+ * how far away at least, is computed once per pixel - conservatively for the whole footprint,
+ * in double interval arithmetic - instead of by the fp32 pre-filter pass of every sample. The
+ * pool kernel's new-path trips read the pixel's record and run only the exact tests, which
+ * take the closest hit over any superset of the true candidates: results do not change.
+ *
+ * rt_camera_primary_table evaluates the table on the host (no device): width * height
+ * records into `out` (`capacity` records), row-major by pixel. A record is
+ *   bits  0-15  candidate mask by primitive slot (rt_camera_export's prims order)
+ *   bits 16-19  slot of the candidate with the smallest bound
+ *   bits 32-47  that candidate's bound on t, fp16
+ *   bits 48-63  one fp16 bound shared by all other candidates (the minimum of theirs)
+ * with bounds >= 0, rounded toward zero; 0 means "always tested". Returns
+ * RT_PRIMARY_TABLE_NONE when the camera does not qualify: a defocus camera (aperture > 0),
+ * more than 16 primitives, or a traversal other than brute force.
+ * rt_camera_primary_table_device returns the records the current device built (building
+ * them if need be): equal to the host's bit for bit.
+ * rt_camera_primary_info: `available` - the camera qualifies; `used` - the most recent render
+ * ran the pool kernel with the table; `built` - its device holds the table; `min_samples` -
+ * samples per pixel from which a render builds it (an existing table is used at any count);
+ * `build_ms` - device time of the builder kernel (waits for it; 0 when not built).
+ * RT_AMD_PRIMARY_TABLE=0 in the environment keeps every launch on the pre-filter pass; =1 uses
+ * the table at any sample count. */
+typedef struct {
+    int32_t available, used, built, min_samples;
+    float build_ms;
+} rt_primary_info;
+int rt_camera_primary_table(const rt_camera* cam, uint64_t* out, int32_t capacity);
+int rt_camera_primary_table_device(rt_camera* cam, uint64_t* out, int32_t capacity);
+int rt_camera_primary_info(rt_camera* cam, rt_primary_info* info);
 
 /* Frees the camera's device resources on every device it rendered on (scene copies, frame,
  * record and slab buffers, streams, events). A camera otherwise keeps one scene copy per device

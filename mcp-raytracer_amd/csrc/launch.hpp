@@ -38,6 +38,8 @@ struct KernelVariant {
     int trav;    // TRAV_FAST / TRAV_REFERENCE / TRAV_BRUTE (resolved, never AUTO)
     bool defer = false;  // TRAV_FAST: deferred exact sphere tests (TRAV_FAST_DEFER kernels)
     bool pool = false;   // chunked passes run the stage-compacted pool kernel (pt_pool_kernel)
+    // pool passes: the primary-ray candidate table (primary.hpp) or null - pt_pool_primary_kernel
+    const uint2* ptab = nullptr;
 };
 
 // sb == nullptr: the sequential-pixel kernel; else the chunked kernel over sb's pass.
@@ -83,11 +85,15 @@ inline size_t stack_lds_bytes(int stack_depth, int trav, int n_prims, bool lds_t
 // pool kernel (product brute-force builds; RT_POOL_PROF adds its ref-precision timer build).
 template <class Real, bool EMIT, int INSTR, int TRAV, int LDSS>
 hipError_t dispatch_kernel(const DevScene& S, const RtRegion& reg, const RenderOut& out, const LaunchGeom& g,
-                           const SampleBuf* sb, bool pool, hipStream_t stream) {
+                           const SampleBuf* sb, bool pool, const uint2* ptab, hipStream_t stream) {
     if (sb && pool) {
         if constexpr (!EMIT && TRAV == TRAV_BRUTE && (INSTR == 0 || (RT_POOL_PROF && INSTR == 2 && sizeof(Real) == 8))) {
-            hipLaunchKernelGGL((pt_pool_kernel<Real, TRAV, LDSS>), dim3(g.grid), dim3(kBlockPool), g.lds_bytes, stream,
-                               S, reg, out, g.tiles_x, *sb);
+            if (ptab)  // with the primary-ray candidate table (primary.hpp)
+                hipLaunchKernelGGL((pt_pool_primary_kernel<Real, TRAV, LDSS>), dim3(g.grid), dim3(kBlockPool),
+                                   g.lds_bytes, stream, S, reg, out, g.tiles_x, *sb, ptab);
+            else
+                hipLaunchKernelGGL((pt_pool_kernel<Real, TRAV, LDSS>), dim3(g.grid), dim3(kBlockPool), g.lds_bytes,
+                                   stream, S, reg, out, g.tiles_x, *sb);
             return hipGetLastError();
         } else {
             return hipErrorInvalidValue;
@@ -104,25 +110,25 @@ hipError_t dispatch_kernel(const DevScene& S, const RtRegion& reg, const RenderO
 
 template <class Real, bool EMIT, int INSTR, int TRAV>
 hipError_t dispatch_level(const DevScene& S, const RtRegion& reg, const RenderOut& out, const LaunchGeom& g,
-                          const SampleBuf* sb, bool pool, hipStream_t stream) {
+                          const SampleBuf* sb, bool pool, const uint2* ptab, hipStream_t stream) {
     // LDS residency levels (pt_kernel.hpp scene_prologue); never with the reference traversal
     constexpr int L1 = trav_fast(TRAV) ? 1 : 0, L2 = TRAV == TRAV_REFERENCE ? 0 : 2;
-    if (g.lds_level >= 2) return dispatch_kernel<Real, EMIT, INSTR, TRAV, L2>(S, reg, out, g, sb, pool, stream);
-    if (g.lds_level == 1) return dispatch_kernel<Real, EMIT, INSTR, TRAV, L1>(S, reg, out, g, sb, pool, stream);
-    return dispatch_kernel<Real, EMIT, INSTR, TRAV, 0>(S, reg, out, g, sb, pool, stream);
+    if (g.lds_level >= 2) return dispatch_kernel<Real, EMIT, INSTR, TRAV, L2>(S, reg, out, g, sb, pool, ptab, stream);
+    if (g.lds_level == 1) return dispatch_kernel<Real, EMIT, INSTR, TRAV, L1>(S, reg, out, g, sb, pool, ptab, stream);
+    return dispatch_kernel<Real, EMIT, INSTR, TRAV, 0>(S, reg, out, g, sb, pool, ptab, stream);
 }
 
 template <class Real, int TRAV>
 hipError_t dispatch_variant(const KernelVariant& v, const DevScene& S, const RtRegion& reg, const RenderOut& out,
                             const LaunchGeom& g, const SampleBuf* sb, hipStream_t stream) {
     if (v.count == 2)
-        return v.emit ? dispatch_level<Real, true, 2, TRAV>(S, reg, out, g, sb, v.pool, stream)
-                      : dispatch_level<Real, false, 2, TRAV>(S, reg, out, g, sb, v.pool, stream);
+        return v.emit ? dispatch_level<Real, true, 2, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream)
+                      : dispatch_level<Real, false, 2, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream);
     if (v.count == 1)
-        return v.emit ? dispatch_level<Real, true, 1, TRAV>(S, reg, out, g, sb, v.pool, stream)
-                      : dispatch_level<Real, false, 1, TRAV>(S, reg, out, g, sb, v.pool, stream);
-    return v.emit ? dispatch_level<Real, true, 0, TRAV>(S, reg, out, g, sb, v.pool, stream)
-                  : dispatch_level<Real, false, 0, TRAV>(S, reg, out, g, sb, v.pool, stream);
+        return v.emit ? dispatch_level<Real, true, 1, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream)
+                      : dispatch_level<Real, false, 1, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream);
+    return v.emit ? dispatch_level<Real, true, 0, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream)
+                  : dispatch_level<Real, false, 0, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream);
 }
 
 template <class Real>

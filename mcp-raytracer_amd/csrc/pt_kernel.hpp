@@ -1471,6 +1471,66 @@ __device__ __forceinline__ uint16_t* lot_column(SK* stk) {
 struct NoHook {
     __device__ void operator()() const {}
 };
+// The brute-force pass's second half: exact tests of the candidates in `mask`, nearest lower
+// bound first, until the next bound exceeds the best hit. `next(mask, kb, lb)` picks the
+// remaining candidate with the smallest bound (never NaN). The result is the lexicographic
+// minimum of (t, slot) over the candidates' exact hits, whatever the order of the tests: any
+// superset of the true candidates with valid lower bounds returns the same hit.
+template <class Real, bool COUNT, class Next>
+__device__ __forceinline__ int brute_nearest_first(const DevScene& S, const RayK<Real>& r, uint32_t mask, Real& t_hit,
+                                                   uint32_t* cnt, Next next) {
+    Real best_t = (Real)__builtin_inf();
+    int best = -1;
+    float thi = __builtin_inff();
+    int n_exact = 0;
+    if (COUNT) {
+        cnt[CT_CAND0] += mask == 0u ? 1u : 0u;
+        cnt[CT_CAND2] += __popc(mask) >= 2 ? 1u : 0u;
+    }
+    while (mask != 0u) {
+        int kb;
+        float lb;
+        next(mask, kb, lb);
+        if (lb > thi) break;  // every remaining candidate's t exceeds the best hit
+        mask &= ~(1u << kb);
+        if (COUNT) {
+            count_exact(cnt);
+            if (++n_exact == 2) cnt[CT_EXACT2]++;
+        }
+        Real t;
+        // ref precision: the ray as is, not ray_at_use - its fp64 conversions may then be
+        // scheduled while the record loads are in flight (13.14 -> 13.11 ms,
+        // profiles/r06/pairs/r06_rayhoist/). The fp32 build keeps ray_at_use: there |d|^2 may be
+        // contracted (fma) differently where make_ray is inlined, and the pool and chunked kernels
+        // must return the same hits (test_pool_kernel_equals_chunked_kernel caught 613 pixels).
+        const bool hit = sizeof(Real) == 8
+                             ? prim_exact_rec<Real>(xrec_load(S.xrec + kb), S.prims[kb], r, t)
+                             : prim_exact_rec<Real>(xrec_load(S.xrec + kb), S.prims[kb], ray_at_use<Real>(r), t);
+        if (hit && (t < best_t || (t == best_t && kb < best))) {
+            best_t = t;
+            best = kb;
+            thi = upper_f<Real>(t);
+        }
+    }
+    t_hit = best_t;
+    return best;
+}
+
+// The closest hit of a primary ray of a pinhole camera from its pixel's record of the
+// primary-ray candidate table (primary.hpp): the candidate mask, the nearest candidate's slot
+// and fp16 bound, and one fp16 bound shared by the others. No fp32 pre-filter pass.
+template <class Real, bool COUNT>
+__device__ __forceinline__ int closest_hit_primary(const DevScene& S, const RayK<Real>& r, Real& t_hit, uint2 rec,
+                                                   uint32_t* cnt) {
+    const int near = (int)((rec.x >> 16) & 15u);
+    const float bn = lot_load((uint16_t)rec.y), bo = lot_load((uint16_t)(rec.y >> 16));
+    return brute_nearest_first<Real, COUNT>(S, r, rec.x & 0xffffu, t_hit, cnt, [&](uint32_t m, int& kb, float& lb) {
+        const bool n = ((m >> near) & 1u) != 0u;  // bn <= bo: the nearest candidate first
+        kb = n ? near : __builtin_ctz(m);
+        lb = n ? bn : bo;
+    });
+}
+
 // `after_prefilter`: called once the pre-filter pass is done (diagnostic section timer).
 template <class Real, bool COUNT, class Hook = NoHook>
 __device__ __forceinline__ int closest_hit_brute_nf(const DevScene& S, int n_prims, const RayK<Real>& r, Real& t_hit,
@@ -1540,19 +1600,11 @@ __device__ __forceinline__ int closest_hit_brute_nf(const DevScene& S, int n_pri
         }
     }
     after_prefilter();
-    Real best_t = (Real)__builtin_inf();
-    int best = -1;
-    float thi = __builtin_inff();
-    int n_exact = 0;
-    if (COUNT) {
-        cnt[CT_CAND0] += mask == 0u ? 1u : 0u;
-        cnt[CT_CAND2] += __popc(mask) >= 2 ? 1u : 0u;
-    }
-    while (mask != 0u) {
+    return brute_nearest_first<Real, COUNT>(S, r, mask, t_hit, cnt, [&](uint32_t rest, int& kb, float& lb) {
         // nearest remaining candidate (stored bounds are never NaN: lot_store)
-        int kb = __builtin_ctz(mask);
-        float lb = lot_load(lot[kb * kStackStride]);
-        for (uint32_t m = mask & (mask - 1u); m != 0u; m &= m - 1u) {
+        kb = __builtin_ctz(rest);
+        lb = lot_load(lot[kb * kStackStride]);
+        for (uint32_t m = rest & (rest - 1u); m != 0u; m &= m - 1u) {
             const int k = __builtin_ctz(m);
             const float l = lot_load(lot[k * kStackStride]);
             if (l < lb) {
@@ -1560,29 +1612,7 @@ __device__ __forceinline__ int closest_hit_brute_nf(const DevScene& S, int n_pri
                 kb = k;
             }
         }
-        if (lb > thi) break;  // every remaining candidate's t exceeds the best hit
-        mask &= ~(1u << kb);
-        if (COUNT) {
-            count_exact(cnt);
-            if (++n_exact == 2) cnt[CT_EXACT2]++;
-        }
-        Real t;
-        // ref precision: the ray as is, not ray_at_use - its fp64 conversions may then be
-        // scheduled while the record loads are in flight (13.14 -> 13.11 ms,
-        // profiles/r06/pairs/r06_rayhoist/). The fp32 build keeps ray_at_use: there |d|^2 may be
-        // contracted (fma) differently where make_ray is inlined, and the pool and chunked kernels
-        // must return the same hits (test_pool_kernel_equals_chunked_kernel caught 613 pixels).
-        const bool hit = sizeof(Real) == 8
-                             ? prim_exact_rec<Real>(xrec_load(S.xrec + kb), S.prims[kb], r, t)
-                             : prim_exact_rec<Real>(xrec_load(S.xrec + kb), S.prims[kb], ray_at_use<Real>(r), t);
-        if (hit && (t < best_t || (t == best_t && kb < best))) {
-            best_t = t;
-            best = kb;
-            thi = upper_f<Real>(t);
-        }
-    }
-    t_hit = best_t;
-    return best;
+    });
 }
 
 // ONBasis (src/geometry/onbasis.ts:18-51)
@@ -2861,9 +2891,27 @@ __device__ __forceinline__ void stack_push(uint8_t* q, bool top, int& cnt, bool 
     cnt += __popcll(m);
 }
 
-template <class Real, int TRAV, int LDSS>
-__global__ __launch_bounds__(kBlockPool) void pt_pool_kernel(DevScene S0, RtRegion reg, RenderOut out, int tiles_x,
-                                                               SampleBuf sb) {
+// The primary-ray candidate table's pointer (pt_pool_primary_kernel's last argument, after
+// pt_pool_kernel's), read through the opaque kernarg pointer where a new-path trip needs it
+// (one scalar load) instead of a register pair live across the trip loop.
+struct KernArgsPrimary {
+    KernArgs args;
+    const uint2* ptab;  // by row-major pixel (primary.hpp)
+};
+__device__ __forceinline__ const uint2* primary_table_opaque() {
+    KArgPtr p = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const uint2* const*)(p + offsetof(KernArgsPrimary, ptab));
+}
+
+// The pool kernel's body, shared by its two entries. PRIM: the trips that start new paths
+// take each primary ray's candidates from the primary-ray table (primary.hpp) instead
+// of running the fp32 pre-filter pass: a trip serves one of the two A stacks, so it is
+// wave-uniformly all primary rays or none, and the branch costs no divergence.
+template <class Real, int TRAV, int LDSS, bool PRIM>
+// (The arguments by value, as the entries take them: by reference the compiler kept them in the
+// kernarg segment and the LDS-resident ref kernel went from 53 to 76 spilled SGPRs.)
+__device__ __forceinline__ void pool_trips(DevScene S0, RtRegion reg, RenderOut out, int tiles_x, SampleBuf sb) {
     extern __shared__ int lds_stack[];
     const RtCamera& C0 = S0.cam;
     __shared__ PhaseRow ptab[kMaxPhases];
@@ -3007,11 +3055,19 @@ __global__ __launch_bounds__(kBlockPool) void pt_pool_kernel(DevScene S0, RtRegi
             if (k >= 0 && phase != PH_ITEM) {
                 const RtCamera& C = cam_opaque();
                 Path<false> P;
+                uint2 prec = make_uint2(0u, 0u);  // PRIM: the pixel's record of the primary-ray table
                 if (phase == PH_NEW) {
                     int i, j;  // the slot's pixel (the hand-out's slot_pixel)
                     slot_pixel(sb, reg, tiles_x, rtx, endX, endY, slot, i, j);
-                    path_begin<Real, false>(C, P, pixel_center<Real>(C, i, j),
-                                            (uint32_t)j * (uint32_t)C.width + (uint32_t)i, (uint32_t)(sb.s_base + s));
+                    const uint32_t pix = (uint32_t)j * (uint32_t)C.width + (uint32_t)i;
+                    if (PRIM) prec = primary_table_opaque()[pix];  // in flight during the path start
+                    path_begin<Real, false>(C, P, pixel_center<Real>(C, i, j), pix, (uint32_t)(sb.s_base + s));
+                    // Wait for the record here, inside the block that issued its load (slot_pixel's
+                    // note): pending on the paths around this block, its registers would make later
+                    // writes of them wait with vmcnt(0), for the sample records stored before them too.
+                    // This is the trip loop's one vector-memory load; on gfx9 the wait also covers the
+                    // previous trip's record stores, which the path start has given time to drain.
+                    if (PRIM) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (gfx9 encoding)
                 } else {
                     P.rng = (uint64_t)__float_as_uint(g0.x) | ((uint64_t)__float_as_uint(g0.y) << 32);
                     P.o = V3{g1.x, g1.y, g1.z};
@@ -3030,7 +3086,10 @@ __global__ __launch_bounds__(kBlockPool) void pt_pool_kernel(DevScene S0, RtRegi
                     const RayK<Real> ray = make_ray<Real>(P.o, P.d);
                     Real t;
                     int h;
-                    if (PP && TRAV == TRAV_BRUTE && C.n_prims <= kBruteMaxPrims)  // section timer
+                    if (PRIM && !atop) {  // the new-path stack: every lane traces a primary ray
+                        psec<PP>(pf, PR_TILE);  // (no pre-filter section)
+                        h = closest_hit_primary<Real, false>(S, ray, t, prec, cnt);
+                    } else if (PP && TRAV == TRAV_BRUTE && C.n_prims <= kBruteMaxPrims)  // section timer
                         h = closest_hit_brute_nf<Real, false>(S, C.n_prims, ray, t, lot_column(stk), cnt,
                                                               [&]() { psec<PP>(pf, PR_TILE); });
                     else
@@ -3095,5 +3154,19 @@ __global__ __launch_bounds__(kBlockPool) void pt_pool_kernel(DevScene S0, RtRegi
     publish_counters<false, PP>(out, cnt, pf, lane);
 }
 
+template <class Real, int TRAV, int LDSS>
+__global__ __launch_bounds__(kBlockPool) void pt_pool_kernel(DevScene S0, RtRegion reg, RenderOut out, int tiles_x,
+                                                               SampleBuf sb) {
+    pool_trips<Real, TRAV, LDSS, false>(S0, reg, out, tiles_x, sb);
+}
+// The pool kernel with the primary-ray candidate table `ptab`: brute-force launches of a
+// pinhole camera with at most kBruteMaxPrims primitives (rt_api.cpp). The trip loop reads
+// `ptab` through primary_table_opaque.
+template <class Real, int TRAV, int LDSS>
+__global__ __launch_bounds__(kBlockPool) void pt_pool_primary_kernel(DevScene S0, RtRegion reg, RenderOut out,
+                                                                       int tiles_x, SampleBuf sb, const uint2* ptab) {
+    (void)ptab;
+    pool_trips<Real, TRAV, LDSS, true>(S0, reg, out, tiles_x, sb);
+}
 
 }  // namespace rt

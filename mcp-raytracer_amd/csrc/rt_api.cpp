@@ -29,6 +29,7 @@
 #include "denoise.hpp"
 #include "json.hpp"
 #include "launch.hpp"
+#include "primary.hpp"
 #include "progressive.hpp"
 #include "scene.hpp"
 
@@ -285,7 +286,22 @@ struct CamHost {
         if (trav == TRAV_AUTO) return build.cam.n_prims <= kBruteMaxPrims ? TRAV_BRUTE : TRAV_FAST;
         return trav;
     }
+    // The primary-ray candidate table (primary.hpp) serves brute-force launches of a pinhole
+    // camera (path_begin moves the origin only when aperture > 0) over at most 16 primitives.
+    bool primary_table_ok(int trav) const {
+        return effective_traversal(trav) == TRAV_BRUTE && !(build.cam.aperture > 0.0) &&
+               build.cam.n_prims <= kPrimaryMaxPrims && (size_t)build.cam.n_prims == build.prims.size();
+    }
 };
+
+// Samples per pixel from which a launch builds the primary-ray candidate table (an existing
+// table is used at any count): the measured break-even of a fresh camera's first render,
+// rounded up to a power of two. Cornell 800x800 on MI355X: the builder kernel takes 0.060 ms
+// and the first render 0.08 ms more than without the table (allocation and events included);
+// the table saves 0.032 ms of a 16-sample frame and 1.30 ms of a 256-sample one, so the first
+// render breaks even at ~25 samples per pixel.
+constexpr int kPrimaryMinSamples = 32;
+constexpr bool kPrimaryDefault = true;  // RT_AMD_PRIMARY_TABLE unset
 
 // One device's copy of a camera: the scene blob in that device's HBM, its frame, record and
 // stats buffers, events and (multi-GPU) its stream and tile-packed slabs. A camera keeps one
@@ -315,6 +331,12 @@ struct DevCtx {
     int n_passes = 0;
     bool ev_accum = false;
     int last_kernel = RT_KERNEL_NONE;
+    // the primary-ray candidate table (primary.hpp): W x H records beside the scene blob, built
+    // on first use (the camera and the primitives never change after rt_camera_create)
+    uint64_t* d_ptab = nullptr;
+    hipEvent_t ptab_ev[2] = {nullptr, nullptr};  // around the builder kernel
+    hipStream_t ptab_stream = nullptr;           // the stream it was queued on
+    bool ptab_used = false;                      // the last launch ran pt_pool_primary_kernel
     unsigned long long* d_stats = nullptr;
     unsigned long long* d_counters = nullptr;
     unsigned int* d_tile = nullptr;
@@ -384,8 +406,12 @@ struct DevCtx {
         (void)hipGetDevice(&prev);
         (void)hipSetDevice(device);
         for (void* p : {(void*)d_blob, (void*)d_stats, (void*)d_counters, (void*)d_tile, (void*)d_rgb, (void*)d_rad,
-                        (void*)d_sbuf})
+                        (void*)d_sbuf, (void*)d_ptab})
             if (p) (void)hipFree(p);
+        d_ptab = nullptr;
+        for (hipEvent_t& e : ptab_ev)
+            if (e) (void)hipEventDestroy(e), e = nullptr;
+        ptab_used = false;
         // every freed pointer is reset: a later ensure_device / ensure_frame /
         // ensure_sbuf (possibly on another device) must reallocate all of them
         d_blob = nullptr;
@@ -661,6 +687,36 @@ struct DevCtx {
         return S;
     }
 
+    // The primary-ray candidate table, built on `stream` at first use; a launch on another
+    // stream waits for the builder.
+    const uint2* ensure_primary_table(hipStream_t stream) {
+        if (!d_ptab) {
+            const RtCamera& C = build.cam;
+            const size_t n = (size_t)C.width * (size_t)C.height;
+            hip_check(hipMalloc(&d_ptab, std::max<size_t>(n, 1) * sizeof(uint64_t)), "hipMalloc(primary table)");
+            for (hipEvent_t& e : ptab_ev)
+                if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+            hip_check(hipEventRecord(ptab_ev[0], stream), "hipEventRecord");
+            hip_check(launch_primary_table(C, reinterpret_cast<const RtPrim*>(reinterpret_cast<const char*>(d_blob) + off_prims),
+                                           C.n_prims, d_ptab, stream),
+                      "primary_table_kernel launch");
+            hip_check(hipEventRecord(ptab_ev[1], stream), "hipEventRecord");
+            ptab_stream = stream;
+        } else if (stream != ptab_stream) {
+            hip_check(hipStreamWaitEvent(stream, ptab_ev[1], 0), "hipStreamWaitEvent");
+        }
+        return reinterpret_cast<const uint2*>(d_ptab);
+    }
+    // Device time of the builder kernel (0 before it ran). Waits for it.
+    float primary_table_ms() {
+        float ms = 0.0f;
+        if (d_ptab && ptab_ev[1]) {
+            hip_check(hipEventSynchronize(ptab_ev[1]), "hipEventSynchronize");
+            hip_check(hipEventElapsedTime(&ms, ptab_ev[0], ptab_ev[1]), "hipEventElapsedTime");
+        }
+        return ms;
+    }
+
     // Launch one render; returns after queueing (and synchronising if asked).
     void launch(const rt_region& region, int tile_group, int tile_groups, int prec, int trav, int count,
                 uint8_t* rgb, float* rad, int32_t* pxs, int32_t* pxb, int packed, hipStream_t stream,
@@ -736,6 +792,7 @@ struct DevCtx {
         hip_check(launch_init_stats(d_stats, count ? d_counters : nullptr, d_tile, stream), "init_stats");
         n_passes = 0;
         last_kernel = RT_KERNEL_NONE;
+        ptab_used = false;
         adapt_rounds = 0;
         adapt_rendered = 0;
         if (mine == 0) return;
@@ -785,6 +842,14 @@ struct DevCtx {
                  build.prims.size() < (1u << 14) &&
                  (size_t)S.lds_pool_off + pool_lds_bytes() + static_lds_bytes(count, true) <= (size_t)lds_max &&
                  env_flag("RT_AMD_POOL_KERNEL", true);
+        // The primary-ray candidate table (primary.hpp) for the pool kernel's new-path trips:
+        // built once the camera renders enough samples per pixel to repay the builder kernel
+        // (kPrimaryMinSamples), used whenever it exists. RT_AMD_PRIMARY_TABLE=0 keeps every launch
+        // on the pre-filter pass, =1 uses the table at any sample count (A/B and the tests).
+        const int primary_env = env_int0("RT_AMD_PRIMARY_TABLE", -1);
+        const bool primary_ok = pool_ok && host.primary_table_ok(trav) &&
+                                (primary_env > 0 || (primary_env < 0 && kPrimaryDefault &&
+                                                     (d_ptab != nullptr || C.n_samples >= kPrimaryMinSamples)));
         // guided schedule of `nsamp` samples over `slots` pixel slots: half of the remaining
         // samples per phase, chunks halving. First-phase chunk from the samples per resident
         // lane: an item is the critical path of its pixel, so small per-launch workloads (a
@@ -889,6 +954,11 @@ struct DevCtx {
             gp.grid = (int)std::max<long>(1, std::min<long>(items / block + 1, (long)cus));
             DevScene Sp = S;
             if (v.pool) gp.lds_bytes = (size_t)S.lds_pool_off + pool_lds_bytes();
+            v.ptab = nullptr;
+            if (v.pool && primary_ok) {  // pt_pool_primary_kernel
+                v.ptab = ensure_primary_table(stream);
+                ptab_used = true;
+            }
             // per-pass events: path kernel [0, 1), accumulate [1, 2)
             hip_check(hipEventRecord(pass_event(pass, 0), stream), "hipEventRecord");
             hipError_t e = prec == PREC_FP32 ? launch_render_fp32(v, Sp, reg, out, gp, &sb, stream)
@@ -2137,6 +2207,65 @@ int rt_camera_last_kernel(rt_camera* cam, int32_t* kernel) {
     std::lock_guard<std::mutex> lock(cam->mu);
     *kernel = cam->last ? cam->last->last_kernel : RT_KERNEL_NONE;
     return RT_OK;
+}
+
+int rt_camera_primary_table(const rt_camera* cam, uint64_t* out, int32_t capacity) {
+    if (!cam || !out) return set_error(RT_ERR_INVALID, "null argument");
+    const RtCamera& C = cam->build.cam;
+    if (!cam->primary_table_ok(cam->traversal))
+        return set_error(RT_PRIMARY_TABLE_NONE,
+                         "no primary-ray table: it needs a pinhole camera (aperture 0) and brute-force traversal "
+                         "of at most 16 primitives");
+    if ((int64_t)capacity < (int64_t)C.width * C.height)
+        return set_error(RT_ERR_INVALID, "rt_camera_primary_table: capacity below width * height records");
+    primary_table_host(C, cam->build.prims.data(), C.n_prims, out);
+    return RT_OK;
+}
+
+int rt_camera_primary_info(rt_camera* cam, rt_primary_info* info) {
+    if (!cam || !info) return set_error(RT_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(cam->mu);
+    try {
+        DevCtx* c = cam->last;
+        info->available = cam->primary_table_ok(cam->traversal) ? 1 : 0;
+        info->used = c && c->ptab_used ? 1 : 0;
+        info->built = c && c->d_ptab ? 1 : 0;
+        info->min_samples = kPrimaryMinSamples;
+        info->build_ms = 0.0f;
+        if (c && c->d_ptab) {
+            DeviceScope scope;
+            hip_check(hipSetDevice(c->device), "hipSetDevice");
+            info->build_ms = c->primary_table_ms();
+        }
+        return RT_OK;
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_DEVICE, e.what());
+    }
+}
+
+int rt_camera_primary_table_device(rt_camera* cam, uint64_t* out, int32_t capacity) {
+    if (!cam || !out) return set_error(RT_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(cam->mu);
+    try {
+        const RtCamera& C = cam->build.cam;
+        if (!cam->primary_table_ok(cam->traversal))
+            return set_error(RT_PRIMARY_TABLE_NONE, "no primary-ray table for this camera");
+        if ((int64_t)capacity < (int64_t)C.width * C.height)
+            throw std::invalid_argument("rt_camera_primary_table_device: capacity below width * height records");
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        c.ensure_primary_table(nullptr);
+        hip_check(hipStreamSynchronize(c.ptab_stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(out, c.d_ptab, (size_t)C.width * C.height * sizeof(uint64_t), hipMemcpyDeviceToHost),
+                  "hipMemcpy(primary table)");
+        return RT_OK;
+    } catch (const HipError& e) {
+        return set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        return set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_RENDER, e.what());
+    }
 }
 
 int rt_multi_plan_region(const rt_region* region, int32_t width, int32_t height, int32_t n_devices,

@@ -101,6 +101,14 @@ class RtDenoiseVarOptions(C.Structure):
 DENOISE_MAX_LEVELS = 8
 
 
+class RtPrimaryInfo(C.Structure):
+    _fields_ = [("available", C.c_int32), ("used", C.c_int32), ("built", C.c_int32), ("min_samples", C.c_int32),
+                ("build_ms", C.c_float)]
+
+
+RT_PRIMARY_TABLE_NONE = 4  # rt_camera_primary_table: the camera has no primary-ray table
+
+
 class RtError(RuntimeError):
     """An error returned through the C ABI (the reference would throw an Error)."""
 
@@ -137,6 +145,9 @@ _SIGS = {
     "rt_camera_stats_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_camera_pass_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_camera_last_kernel": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "rt_camera_primary_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "rt_camera_primary_table_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "rt_camera_primary_info": (C.c_int, [C.c_void_p, C.POINTER(RtPrimaryInfo)]),
     "rt_camera_release_device": (C.c_int, [C.c_void_p]),
     "rt_build_id": (C.c_char_p, []),
     "rt_tiles_unpack": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RtRegion), C.c_int32, C.c_int32,

@@ -363,6 +363,33 @@ class Camera:
         _lib.check(self._lib.rt_camera_last_kernel(self._h, C.byref(n)))
         return self.KERNELS[int(n.value)]
 
+    # -- the primary-ray candidate table --------------------------------------------
+    def primary_table(self, device: bool = False):
+        """The pool kernel's primary-ray candidate table (rt_camera_primary_table): a uint64
+        (height, width) array, one record per pixel - candidate mask (bits 0-15), nearest
+        candidate's slot (16-19) and fp16 bound (32-47), the other candidates' shared fp16
+        bound (48-63). Evaluated on the host; `device=True` returns the records the current
+        device built. None when the camera has no table (defocus, more than 16 primitives, or
+        a traversal other than brute force)."""
+        import numpy as np
+        w, h = self.info["width"], self.info["height"]
+        out = np.zeros((h, w), np.uint64)
+        fn = self._lib.rt_camera_primary_table_device if device else self._lib.rt_camera_primary_table
+        code = fn(self._h, out.ctypes.data, int(out.size))
+        if code == _lib.RT_PRIMARY_TABLE_NONE:
+            return None
+        _lib.check(code)
+        return out
+
+    def primary_info(self) -> dict:
+        """rt_camera_primary_info: {"available": the camera qualifies for the table, "used": the
+        last render's pool kernel read it, "built": the device holds it, "min_samples": samples
+        per pixel from which a render builds it, "build_ms": the builder kernel's device time}."""
+        i = _lib.RtPrimaryInfo()
+        _lib.check(self._lib.rt_camera_primary_info(self._h, C.byref(i)))
+        return {"available": bool(i.available), "used": bool(i.used), "built": bool(i.built),
+                "min_samples": int(i.min_samples), "build_ms": float(i.build_ms)}
+
     # -- progressive rendering -------------------------------------------------
     def progressive(self, region=None) -> "ProgressiveRender":
         """Open a progressive session over `region` (default: the whole image) at zero

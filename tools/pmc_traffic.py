@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fold rocprofv3 FETCH_SIZE / WRITE_SIZE passes into profiles/pmc_traffic.json.
 
-Per configuration: the dominant kernel's (pt_pool_kernel, else pt_chunk_kernel, else
+Per configuration: the dominant kernel's (pt_pool_primary_kernel / pt_pool_kernel, else pt_chunk_kernel, else
 pt_render_kernel; product build INSTR=0) counters averaged over its dispatches,
 times the dispatches per render of a multi-pass launch (roofline.passes). FETCH_SIZE and
 WRITE_SIZE are in KiB. gfx950 correction (MI355X_MICROARCH.md, HBM section):
@@ -28,11 +28,11 @@ def kernel_avg(csv_path, counter):
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     for r in csv.DictReader(open(csv_path)):
         name = r["Kernel_Name"]
-        m = re.search(r"(pt_pool_kernel|pt_chunk_kernel|pt_render_kernel|pt_accum_kernel)<?([^>(]*)", name)
+        m = re.search(r"(pt_pool_primary_kernel|pt_pool_kernel|pt_chunk_kernel|pt_render_kernel|pt_accum_kernel)<?([^>(]*)", name)
         if not m or r["Counter_Name"] != counter:
             continue
         tmpl = m.group(2)
-        if m.group(1) not in ("pt_accum_kernel", "pt_pool_kernel") and ", 0, " not in tmpl:
+        if m.group(1) not in ("pt_accum_kernel", "pt_pool_kernel", "pt_pool_primary_kernel") and ", 0, " not in tmpl:
             continue  # instrumented builds (the pool kernel has product builds only)
         per[m.group(1)][r["Dispatch_Id"]] += float(r["Counter_Value"])
     return {k: sum(v.values()) / len(v) for k, v in per.items() if v}
@@ -45,7 +45,7 @@ for n, args in enumerate(cfgs, 1):
     line = json.loads([x for x in log.splitlines() if x.startswith("{")][-1])
     cfg = line["config"]
     key = f"{cfg['scene']}_{cfg['width']}x{cfg['height']}_spp{cfg['spp']}_d{cfg['depth']}_{cfg['precision']}_n{line['n_gpus']}{'_adaptive' if cfg.get('adaptive') else ''}"
-    dom = next((k for k in ("pt_pool_kernel", "pt_chunk_kernel") if k in fetch), "pt_render_kernel")
+    dom = next((k for k in ("pt_pool_primary_kernel", "pt_pool_kernel", "pt_chunk_kernel") if k in fetch), "pt_render_kernel")
     # per RENDER (the bench line's roofline divides by the whole launch's kernel time):
     # a multi-pass launch makes `passes` dispatches of the path kernel per render
     passes = int(line.get("roofline", {}).get("passes") or 1)

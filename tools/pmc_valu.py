@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fold the VALU counter passes (tools/pmc_valu.sh) into profiles/pmc_valu.json.
 
-Per configuration, for the dominant product kernel (pt_pool_kernel, else
+Per configuration, for the dominant product kernel (pt_pool_primary_kernel / pt_pool_kernel, else
 pt_chunk_kernel, else pt_render_kernel; INSTR=0 build), counters averaged over
 its dispatches and the dispatch duration from the same runs' kernel traces.
 Per-sample figures are per RENDER: a multi-pass launch (record budget) makes
@@ -36,6 +36,8 @@ F64_PEAK, F32_PEAK, SIMDS = 78.6, 157.3, 1024
 
 
 def dominant(name):
+    if re.search(r"pt_pool_primary_kernel<", name):
+        return "pt_pool_primary_kernel"  # the pool kernel with the primary-ray table (product-only)
     if re.search(r"pt_pool_kernel<", name):
         return "pt_pool_kernel"  # product-only kernel
     m = re.search(r"(pt_chunk_kernel|pt_render_kernel)<([^>(]*)>", name)
@@ -74,7 +76,7 @@ for n, args in enumerate(cfgs, 1):
         if not pd.is_dir():
             continue
         for (k, _), cs in pass_counters(pd).items():
-            kern = k if kern is None or k in ("pt_chunk_kernel", "pt_pool_kernel") else kern
+            kern = k if kern is None or k in ("pt_chunk_kernel", "pt_pool_kernel", "pt_pool_primary_kernel") else kern
             for c, v in cs.items():
                 acc[(k, c)].append(v)
         for k, v in pass_durations(pd).items():
