@@ -182,6 +182,43 @@ int rt_debug_fp64(int32_t n, const double* x, double* out);
 int rt_debug_pass_plan(int64_t units, int64_t unit_slots, int64_t chunks_per_slot, int64_t rec_bytes_per_unit,
                        int64_t budget_bytes, int64_t* pass_units);
 
+/* The scene blob a device context uploads (host only, no device): the bytes of every section in
+ * upload order, and in `info` the byte offset of each section (all multiples of 16; off_tsph2 is
+ * -1 without leaf-order sphere records), the 16-byte word counts of the two LDS-resident
+ * prefixes, the pre-filter record and planar-basis counts and the total size. `out` may be NULL
+ * (size query); otherwise `capacity` must hold info->bytes. */
+typedef struct {
+    int64_t bytes;
+    int32_t off_tprims, off_tsph, off_prims, off_xrec, off_mats, off_lights, off_onbs, off_nodes, off_pre, off_tsph2;
+    int32_t lds_words, lds_words2, n_pre, n_onb;
+} rt_scene_blob_info;
+int rt_debug_scene_blob(const rt_camera* cam, uint8_t* out, int64_t capacity, rt_scene_blob_info* info);
+
+/* What a render of `region` (tile group `tile_group` of `tile_groups`) would launch on a device
+ * of `cus` compute units and `lds_max` bytes of workgroup LDS (host only, no device): the path kernel (RT_KERNEL_*; NONE: the region is empty), the LDS
+ * residency level and bytes, the traversal stack's bytes, the cached tree top, the defer / pool /
+ * primary-table / 12-byte-record switches, the first pass's grid, the guided schedule and the
+ * pass sizing (units of 64 slots per pass, pass count). Adaptive launches report their first
+ * round. precision < 0: the camera's; count: rt_launch.count_work. `table_exists` is the one
+ * field read: set it to 1 to plan as a context that has already built the table, else to 0. */
+#define RT_PLAN_MAX_PHASES 8
+typedef struct {
+    int32_t table_exists; /* in */
+    rt_region region; /* clamped to the image */
+    int32_t kernel, traversal, tiles;
+    int32_t lds_level, n_top;
+    int64_t lds_bytes, stack_bytes;
+    int32_t defer, pool, primary_ok, rec12;
+    int32_t grid;
+    int32_t sb_pool, n_phases, s0[RT_PLAN_MAX_PHASES], chunk[RT_PLAN_MAX_PHASES], nch[RT_PLAN_MAX_PHASES];
+    int32_t refill_min, min_ready;
+    int32_t samples; /* samples per slot the schedule covers (an adaptive launch: its first round) */
+    int32_t passes;
+    int64_t pass_units;
+} rt_launch_plan;
+int rt_debug_launch_plan(const rt_camera* cam, const rt_region* region, int32_t tile_group, int32_t tile_groups,
+                         int32_t cus, int32_t lds_max, int32_t precision, int32_t count, rt_launch_plan* out);
+
 /* The path RNG stream (seeded Math.random replacement), host evaluation. */
 int rt_debug_rng(uint32_t seed, uint32_t pixel, uint32_t sample, int32_t n, uint32_t* out);
 

@@ -2468,7 +2468,7 @@ struct AdaptRound {
     int32_t* next_act;      // the pixels still sampling after this round
     unsigned int* next_count;  // [0]: pixels carried; [1]: those likely to converge by `horizon`
     int32_t len;            // samples of this round
-    int32_t horizon;        // sample count the round-length rule asks about (rt_api.cpp)
+    int32_t horizon;        // sample count the round-length rule asks about (dev_ctx.cpp)
 };
 
 // One 16-byte sample record; NT: a non-temporal store. The pool kernel's records (read once,
@@ -3160,7 +3160,7 @@ __global__ __launch_bounds__(kBlockPool) void pt_pool_kernel(DevScene S0, RtRegi
     pool_trips<Real, TRAV, LDSS, false>(S0, reg, out, tiles_x, sb);
 }
 // The pool kernel with the primary-ray candidate table `ptab`: brute-force launches of a
-// pinhole camera with at most kBruteMaxPrims primitives (rt_api.cpp). The trip loop reads
+// pinhole camera with at most kBruteMaxPrims primitives (launch_plan.cpp). The trip loop reads
 // `ptab` through primary_table_opaque.
 template <class Real, int TRAV, int LDSS>
 __global__ __launch_bounds__(kBlockPool) void pt_pool_primary_kernel(DevScene S0, RtRegion reg, RenderOut out,

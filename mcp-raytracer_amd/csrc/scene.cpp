@@ -1048,7 +1048,7 @@ struct SahBuilder {
     // runs at the lanes that hold it; spheres-100k 2048^2 spp16 with the fp64 leaf records: leaves
     // <= 4: 33.6 ms, <= 2: 32.1, 1: 30.1) and small ones (< 100 primitives; rain-50 1080p spp128:
     // 11.09 -> 10.91 ms). LDS-resident trees of 100 .. 1,024 primitives run the deferred exact tests
-    // (rt_api.cpp v.defer), whose leaf loop is cheap per primitive: they keep <= 4 / 2 (spheres-500:
+    // (launch_plan.cpp v.defer), whose leaf loop is cheap per primitive: they keep <= 4 / 2 (spheres-500:
     // leaves of 1 5.72 -> 5.76 ms, of <= 2 7.27 ms) (profiles/r05/sah/).
     bool one_leaf = pbox.size() > 1024 || pbox.size() < 100;
     double trav_cost = env_double("RT_AMD_SAH_CT", 1.0);

@@ -114,7 +114,7 @@ static_assert(sizeof(RtMat) == 64, "RtMat must be 64 bytes");
 //   PRE_SPHERE2 {cx0, cx1, cy0, cy1, cz0, cz1, r0, r1, r0^2, r1^2};
 //   PRE_QUAD2 + code {x_a, sv, su, -Q[ia]*sv - 1/2, -Q[ib]*su - 1/2, -|sv|, -|su|} as element pairs,
 //   then max(kRel max(|Q[ia]|, |Q[ib]|)) of the two.
-// (scene.cpp encode_axis_quad, rt_api.cpp prefilter_records)
+// (scene.cpp encode_axis_quad, scene_blob.cpp prefilter_records)
 enum : int32_t { PRE_SPHERE = 0, PRE_OTHER = 7, PRE_SPHERE2 = 8, PRE_QUAD2 = 8 /* + code 1..6 */ };
 struct alignas(16) RtPre {
     float f[15];

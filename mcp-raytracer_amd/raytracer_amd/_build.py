@@ -56,12 +56,20 @@ _UNITS = [
     ("primary.hip", ["-ffp-contract=off"], True),
     ("frame.hip", [], True),
     ("png.hip", [], True),
+    # the C ABI and the host side of a launch: compiled as HIP for pt_kernel.hpp's types
     ("rt_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("dev_ctx.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("launch_plan.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("multi_gpu.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    # plain C++ (no device, no HIP runtime)
     ("scene.cpp", ["-ffp-contract=off"], False),
+    ("scene_blob.cpp", ["-ffp-contract=off"], False),
+    ("prog_blob.cpp", ["-ffp-contract=off"], False),
     ("image.cpp", [], False),
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "png_deflate.hpp", "primary.hpp"]
+            "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "dev_ctx.hpp"]
 _LIBS = ["-lz"]
 
 

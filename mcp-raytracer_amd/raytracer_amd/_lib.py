@@ -109,6 +109,27 @@ class RtPrimaryInfo(C.Structure):
 RT_PRIMARY_TABLE_NONE = 4  # rt_camera_primary_table: the camera has no primary-ray table
 
 
+class RtSceneBlobInfo(C.Structure):
+    _fields_ = [("bytes", C.c_int64)] + [(n, C.c_int32) for n in (
+        "off_tprims", "off_tsph", "off_prims", "off_xrec", "off_mats", "off_lights", "off_onbs", "off_nodes",
+        "off_pre", "off_tsph2", "lds_words", "lds_words2", "n_pre", "n_onb")]
+
+
+PLAN_MAX_PHASES = 8  # RT_PLAN_MAX_PHASES
+KERNEL = {0: "none", 1: "sequential", 2: "chunked", 3: "pool"}  # RT_KERNEL_*
+
+
+class RtLaunchPlan(C.Structure):
+    _fields_ = [("table_exists", C.c_int32), ("region", RtRegion),
+                ("kernel", C.c_int32), ("traversal", C.c_int32), ("tiles", C.c_int32),
+                ("lds_level", C.c_int32), ("n_top", C.c_int32), ("lds_bytes", C.c_int64), ("stack_bytes", C.c_int64),
+                ("defer", C.c_int32), ("pool", C.c_int32), ("primary_ok", C.c_int32), ("rec12", C.c_int32),
+                ("grid", C.c_int32), ("sb_pool", C.c_int32), ("n_phases", C.c_int32),
+                ("s0", C.c_int32 * PLAN_MAX_PHASES), ("chunk", C.c_int32 * PLAN_MAX_PHASES),
+                ("nch", C.c_int32 * PLAN_MAX_PHASES), ("refill_min", C.c_int32), ("min_ready", C.c_int32),
+                ("samples", C.c_int32), ("passes", C.c_int32), ("pass_units", C.c_int64)]
+
+
 class RtError(RuntimeError):
     """An error returned through the C ABI (the reference would throw an Error)."""
 
@@ -136,6 +157,9 @@ _SIGS = {
     "rt_debug_world_hit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_pass_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                      C.POINTER(C.c_int64)]),
+    "rt_debug_scene_blob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RtSceneBlobInfo)]),
+    "rt_debug_launch_plan": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(RtLaunchPlan)]),
     "rt_debug_rng": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p]),
     "rt_debug_math": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p]),
     "rt_debug_fp64": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p]),
@@ -261,6 +285,34 @@ def multi_plan(region, width: int, height: int, n_devices: int) -> dict:
             "slab_tiles": p.slab_tiles, "tiles": p.tiles, "slab_bytes_rgb": p.slab_bytes_rgb,
             "slab_bytes_radiance": p.slab_bytes_radiance, "stats_offset": p.stats_offset,
             "group_tiles": list(p.group_tiles)[:p.n_devices]}
+
+
+def scene_blob(cam_handle) -> tuple[bytes, dict]:
+    """rt_debug_scene_blob: the scene blob a device context would upload for the camera, and its
+    section offsets and counts (host only)."""
+    info = RtSceneBlobInfo()
+    check(load().rt_debug_scene_blob(cam_handle, None, 0, C.byref(info)))
+    buf = C.create_string_buffer(max(int(info.bytes), 1))
+    check(load().rt_debug_scene_blob(cam_handle, buf, int(info.bytes), C.byref(info)))
+    return buf.raw[:info.bytes], {n: int(getattr(info, n)) for n, _ in RtSceneBlobInfo._fields_}
+
+
+def launch_plan(cam_handle, region, tile_group: int = 0, tile_groups: int = 1, cus: int = 256, lds_max: int = 163840,
+                precision: int = -1, count: int = 0, table_exists: bool = False) -> dict:
+    """rt_debug_launch_plan: what a render of `region` would launch on a device of `cus` compute
+    units and `lds_max` bytes of LDS (host only); the schedule arrays cut to n_phases."""
+    p = RtLaunchPlan()
+    p.table_exists = 1 if table_exists else 0
+    reg = RtRegion(*[int(v) for v in region])
+    check(load().rt_debug_launch_plan(cam_handle, C.byref(reg), int(tile_group), int(tile_groups), int(cus),
+                                      int(lds_max), int(precision), int(count), C.byref(p)))
+    d = {}
+    for n, _ in RtLaunchPlan._fields_[2:]:
+        v = getattr(p, n)
+        d[n] = [int(x) for x in v][:p.n_phases] if n in ("s0", "chunk", "nch") else int(v)
+    d["kernel"] = KERNEL[p.kernel]
+    d["region"] = [p.region.x, p.region.y, p.region.width, p.region.height]
+    return d
 
 
 def progressive_blob_info(blob: bytes) -> dict:

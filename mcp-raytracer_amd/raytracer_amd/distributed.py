@@ -53,7 +53,7 @@ def slab_pixels(region, world: int) -> int:
 
 
 def stats_from_words(w):
-    """RenderStats from the 8 stats words (read_stats in rt_api.cpp)."""
+    """RenderStats from the 8 stats words (stats_from_words in dev_ctx.cpp)."""
     import math
 
     from .camera import RenderStats, _mm

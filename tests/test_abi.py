@@ -277,7 +277,7 @@ def test_device_png_encoder_filters_and_blocks(rt):
 
 def test_pass_plan_caps_items_at_the_counter_headroom(rt):
     """a record budget past the int32 hand-out counter's headroom gives more,
-    bounded passes instead of the 'chunked pass too large' error (rt_api.cpp pass_units).
+    bounded passes instead of the 'chunked pass too large' error (launch_plan.cpp pass_units).
     Config 5 (4096^2, spp 1024: 262,144 tiles; a 1-sample-chunk schedule numbers up to 1,024
     items per slot) at the 32 GB budget that failed in round 4 (profiles/r04/sbuf/)."""
     from raytracer_amd import _lib

@@ -303,7 +303,7 @@ def test_multi_plan_rejects_bad_device_counts(rt):
 
 def test_multi_stats_merge_matches_renderstats_merge(rt):
     """The merge rt_camera_render_multi applies to the devices' stats words (merge_stats_words,
-    rt_api.cpp) is RenderStats.merge (renderStats.ts:42-64): restated here over random words and
+    multi_gpu.cpp) is RenderStats.merge (renderStats.ts:42-64): restated here over random words and
     compared with the Python merge bench.py's per-rank path runs (distributed.merge_stats_words)."""
     import torch
     from raytracer_amd import distributed as rtd

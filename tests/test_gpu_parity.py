@@ -441,7 +441,7 @@ def test_axis_quad_edges_and_corners(rt, oracle, gpu):
 
 
 def _pair_scene():
-    """16 primitives for the brute-force pre-filter's records (rt_api.cpp prefilter_records):
+    """16 primitives for the brute-force pre-filter's records (scene_blob.cpp prefilter_records):
     axis-aligned quads of all six axis codes (u / v swapped gives the second code of an axis),
     three of one code (a pair and a single), two of another on the same plane, five spheres (two
     pairs and a single, one of them a light), a tilted quad and a plane (single records that
@@ -614,7 +614,7 @@ def test_pool_kernel_equals_chunked_kernel(rt, gpu, case, monkeypatch):
 ])
 def test_pool_host_gates_fall_back_bit_exact(rt, oracle, gpu, ro, kernel):
     """The pool kernel packs the bounce phase into 8 bits and the sample index
-    into 16 (pt_kernel.hpp pool_meta / pool_hs); rt_api.cpp gates it on
+    into 16 (pt_kernel.hpp pool_meta / pool_hs); launch_plan.cpp gates it on
     depth <= 250 and spp <= 65535. On each side of both gates the default path
     picks the expected kernel and matches the oracle bit for bit."""
     sd = rt.generate_scene_data({"type": "cornell"})
@@ -641,7 +641,7 @@ def _cornell_plus_spheres(n_extra):
 def test_pool_lds_budget_gate_falls_back_bit_exact(rt, oracle, gpu, n_extra, kernel):
     """The pool kernel's LDS: fp16 candidate columns (primitives x 1024 x 2 B) + the level-2
     scene + 16 waves x 152 path slots. Cornell + 1 sphere (9 primitives) still fits; Cornell +
-    8 (16 primitives: 32 KB of columns) does not, and rt_api.cpp's gate must hand the launch
+    8 (16 primitives: 32 KB of columns) does not, and launch_plan.cpp's gate must hand the launch
     to the chunked kernel - the same image either way."""
     sd = _cornell_plus_spheres(n_extra)
     ro = {"width": 48, "aspect": 1, "samples": 8, "depth": 10, **NOADAPT}
@@ -895,7 +895,7 @@ def test_config5_spheres100k_spp1024_full_frame(rt, oracle, gpu):
 
 
 def test_multipass_chunked_equals_single_pass(rt, gpu, monkeypatch):
-    """A small record budget forces several chunked passes (rt_api.cpp launch loop);
+    """A small record budget forces several chunked passes (dev_ctx.cpp launch_fixed);
     the image, stats and per-pass kernel timing must be the single-pass ones."""
     sd = rt.generate_scene_data({"type": "cornell"})
     ro = {"width": 96, "samples": 37, "depth": 16, **NOADAPT}
@@ -1128,7 +1128,7 @@ def test_rccl_gather_of_tile_groups_assembles_the_frame(gpu, groups, scene):
 
 
 # ---------------------------------------------------------------------------
-# Adaptive sampling in rounds (rt_api.cpp launch_adaptive_rounds, pt_adapt_kernel):
+# Adaptive sampling in rounds (dev_ctx.cpp launch_adaptive_rounds, pt_adapt_kernel):
 # the chunked / pool kernels render each round's samples speculatively, the adapt
 # pass settles them in sample order with the reference's convergence check after
 # every sample (src/camera.ts:348-368,400-425). Same pixels, same stats as the
