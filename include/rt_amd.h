@@ -568,6 +568,80 @@ int rt_camera_denoise_variance(rt_camera* cam, const rt_region* region, const rt
 int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_options* options, uint8_t* rgb,
                                            float* radiance, float* variance_out);
 
+/* ---- Reprojection of a previous view's frame into a new camera view --------------------------
+ * No reference counterpart (the reference renders every frame from scratch). Opt-in like the two
+ * blocks above: no other call changes.
+ *
+ * A service re-renders one scene from a moved camera. On Lambertian and emissive surfaces the
+ * radiance leaving a point does not depend on the viewer, so the previous view's converged
+ * frame is a history for the new view's first frames. Per pixel of the new region, with guides
+ * n, P, D (distance), o (object): no history when o < 0, o >= n_objects, reusable[o] == 0 or P
+ * is not finite. Otherwise P is projected into the previous view V = {center c, pixel00 p, du,
+ * dv, width, height} (the vectors the guide pass builds its rays from), in fp32:
+ *     a = p - c, w = cross(du, dv), aw = a.w, iu = 1 / du.du, iv = 1 / dv.dv      (per view)
+ *     d = P - c, s = aw / d.w, q = d s - a, fi = (q.du) iu, fj = (q.dv) iv
+ * no history unless s is finite and > 0, and fi, fj are finite with -1 < fi < width,
+ * -1 < fj < height. The four bilinear taps at (floor(fi) + dx, floor(fj) + dy), dy outer, weigh
+ * b = (dx ? ax : 1 - ax) (dy ? ay : 1 - ay); a tap counts iff it lies inside the previous image
+ * and prev_region, shows the same object, has finite radiance, n.n' >= normal_min and
+ * |n.(P' - P)| <= sigma_plane D. ws = sum b, acc = sum b c' over the taps that count;
+ * weight = ws if ws >= min_weight else 0; history = acc / ws where weight > 0, else 0.
+ * With a fresh `radiance` c and m = the pixel's own sample count (px_samples, or the scalar
+ * `samples` when px_samples is NULL) as a float, Nh = history_samples:
+ *     weight > 0, c finite, m > 0:  out = (history Nh + c m) / (Nh + m)
+ *     weight > 0 otherwise:         out = history
+ *     weight == 0:                  out = c
+ * and rgb_out is the frame's own u8 of out. Built from fp32 add, subtract, multiply, IEEE divide
+ * and floor in a fixed order, no fused multiply-add, dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z:
+ * the result equals the NumPy restatement tests/reproject_ref.py (the normative definition) in
+ * every bit.
+ *
+ * Limits. The guides are pinhole first hits: view-dependent surfaces (metal, glass, mixed,
+ * layered: reusable = 0) and misses get no history, and a defocus camera's blur is not in them.
+ * The lighting must not have changed between the views. The history is weighted by the constant
+ * history_samples, whatever the previous frame's own sample counts.
+ *
+ * Buffers as the denoise block: HOST buffers in full-frame layout of their own image (the new
+ * frame's width x height, the previous view's width x height), only `region` / `prev_region`
+ * (NULL: the whole image) read and written, outputs may be NULL (radiance_out / rgb_out need
+ * `radiance`). history_out: width*height*3 floats, weight_out: width*height floats.
+ * RT_ERR_INVALID for negative or non-finite options, negative `samples`, a region that is empty
+ * after clamping and a missing required pointer - before any device call.
+ * rt_camera_release_device frees every device buffer of the camera calls. */
+typedef struct { float center[3], pixel00[3], du[3], dv[3]; int32_t width, height; } rt_view;
+typedef struct { float normal_min, sigma_plane, min_weight, history_samples; } rt_reproject_options;   /* NULL or a zero field = default (0.9, 0.01, 0.25, 32) */
+/* The camera's view: the RtCamera vectors in fp32 (host only). */
+int rt_camera_get_view(const rt_camera* cam, rt_view* view);
+/* reusable[o] = 1 iff SceneData.objects[o]'s resolved material (ids followed) is lambert or
+ * light; out holds rt_camera_info.n_objects bytes (capacity below that: RT_ERR_INVALID). Host only. */
+int rt_camera_reusable_objects(const rt_camera* cam, uint8_t* out, int32_t capacity);
+/* explicit buffers, no camera (the calling thread's current device) */
+int rt_reproject(int32_t width, int32_t height, const rt_region* region, const float* normal, const float* position,
+                 const float* distance, const int32_t* object, const rt_view* prev_view, const rt_region* prev_region,
+                 const float* prev_radiance, const float* prev_normal, const float* prev_position,
+                 const float* prev_distance, const int32_t* prev_object, const uint8_t* reusable, int32_t n_objects,
+                 const rt_reproject_options* options, const float* radiance, const int32_t* px_samples, int32_t samples,
+                 float* history_out, float* weight_out, float* radiance_out, uint8_t* rgb_out);
+/* Both cameras' guides are computed on the calling thread's device and never reach the host;
+ * the view and the reusable table are prev_cam's and cam's own. The two cameras must hold the
+ * same scene (flattened nodes, primitives, materials, lights and the object map), else
+ * RT_ERR_INVALID "reproject: the cameras hold different scenes", decided on the host. */
+int rt_camera_reproject(rt_camera* cam, const rt_region* region, rt_camera* prev_cam, const rt_region* prev_region,
+                        const rt_reproject_options* options, const float* prev_radiance, const float* radiance,
+                        const int32_t* px_samples, int32_t samples, float* history_out, float* weight_out,
+                        float* radiance_out, uint8_t* rgb_out);
+/* The open progressive session's device frame blended with the history over the session's
+ * region, each pixel with its own px_samples: nothing is uploaded but the previous radiance.
+ * The session's state, frame and stats are not touched (as rt_camera_progressive_denoise).
+ * RT_ERR_INVALID without an open session and in mode bounces / samples. */
+int rt_camera_progressive_reproject(rt_camera* cam, rt_camera* prev_cam, const rt_region* prev_region,
+                                    const rt_reproject_options* options, const float* prev_radiance, uint8_t* rgb,
+                                    float* radiance, float* weight_out);
+/* Device time of the camera's last rt_camera_reproject / rt_camera_progressive_reproject from
+ * HIP events: the guide passes (both views'; a session reuses its own), the gather kernel, and
+ * the whole span guide passes .. unpacked outputs (host copies excluded). Waits for the events. */
+int rt_camera_reproject_times(rt_camera* cam, float* guide_ms, float* reproject_ms, float* total_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,12 @@ void DevCtx::release() {
         if (e) (void)hipEventDestroy(e), e = nullptr;
     dn_ev.clear();
     dn_levels = 0;
+    rp_prev.free();
+    d_reusable.reset();
+    for (hipEvent_t& e : rp_ev)
+        if (e) (void)hipEventDestroy(e), e = nullptr;
+    rp_ev.clear();
+    rp_timed = false;
     d_acount.reset();
     if (h_acount) (void)hipHostFree(h_acount);
     h_acount = nullptr;
@@ -514,6 +520,25 @@ void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides
     hip_check(launch_guides(dev_scene(), tr, RtRegion{r.x, r.y, r.width, r.height, 0, 1}, d_prim_object, g, lds_max,
                             stream),
               "guide_kernel launch");
+}
+
+hipEvent_t* DevCtx::rp_events() {
+    while (rp_ev.size() < 5) {
+        hipEvent_t e = nullptr;
+        hip_check(hipEventCreate(&e), "hipEventCreate");
+        rp_ev.push_back(e);
+    }
+    return rp_ev.data();
+}
+
+const uint8_t* DevCtx::ensure_reusable() {
+    if (!d_reusable) {
+        std::vector<uint8_t> t = host.reusable_objects();
+        t.resize(std::max<size_t>(t.size(), 1), 0);
+        d_reusable.ensure(t.size(), "hipMalloc(reusable objects)");
+        hip_check(hipMemcpy(d_reusable, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    }
+    return d_reusable;
 }
 
 void DevCtx::ensure_adapt(size_t slots) {

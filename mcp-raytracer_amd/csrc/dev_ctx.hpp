@@ -20,6 +20,7 @@
 #include "launch_plan.hpp"
 #include "primary.hpp"
 #include "progressive.hpp"
+#include "reproject.hpp"
 #include "scene.hpp"
 #include "scene_blob.hpp"
 
@@ -71,6 +72,17 @@ struct CamHost {
         if (!build.fast_ok) return TRAV_REFERENCE;
         if (trav == TRAV_AUTO) return build.cam.n_prims <= kBruteMaxPrims ? TRAV_BRUTE : TRAV_FAST;
         return trav;
+    }
+    // reusable[o] = 1 iff SceneData.objects[o]'s material (already resolved to a table index by
+    // the build) is lambert or light: what a reprojection may carry over to another view.
+    std::vector<uint8_t> reusable_objects() const {
+        std::vector<uint8_t> t((size_t)std::max(build.cam.n_prims, 0), 0);
+        for (size_t s = 0; s < build.prims.size() && s < build.prim_object.size(); ++s) {
+            const int32_t o = build.prim_object[s], m = build.prims[s].mat;
+            if (o < 0 || (size_t)o >= t.size() || m < 0 || (size_t)m >= build.mats.size()) continue;
+            t[o] = build.mats[m].type == MAT_LAMBERT || build.mats[m].type == MAT_LIGHT;
+        }
+        return t;
     }
     // The primary-ray candidate table (primary.hpp) serves brute-force launches of a pinhole
     // camera (path_begin moves the origin only when aperture > 0) over at most 16 primitives.
@@ -219,6 +231,20 @@ struct DevCtx {
 
     // The guide pass over `r` (clamped) into g, through the strategy `trav` resolves to; queued.
     void launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream);
+
+    // ---- Reprojection (reproject.hpp) -----------------------------------------------------------
+    // As the NEW view's context: the reusable table and the events of the last call. As the
+    // PREVIOUS view's context: that view's guides (gn / gp), its uploaded radiance (rad()) and
+    // packed colour (c0) - buffers of their own, so a camera may be both views of one call.
+    DnBufs rp_prev;
+    DevBuf<uint8_t> d_reusable;      // object index -> 1: lambert or light
+    // HIP events of the last reproject call: start, after the guide passes, before and after
+    // the gather kernel, after the unpack passes
+    std::vector<hipEvent_t> rp_ev;
+    bool rp_timed = false;           // a call has recorded them
+    hipEvent_t* rp_events();
+    // The reusable table on the device (uploaded once: the scene never changes).
+    const uint8_t* ensure_reusable();
 
     int adapt_rounds = 0;                   // rounds of the last adaptive render
     unsigned long long adapt_rendered = 0;  // samples its rounds rendered (>= the samples kept)

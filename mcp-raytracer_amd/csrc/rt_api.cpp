@@ -222,6 +222,32 @@ static int camera_call(rt_camera* cam, F&& f) {
     }
 }
 
+// Runs f under both cameras' locks (one lock when they are the same camera), with the
+// single-device entries' error mapping.
+template <class F>
+static int two_camera_call(rt_camera* cam, rt_camera* prev_cam, F&& f) {
+    if (!cam || !prev_cam) return set_error(RT_ERR_INVALID, "null camera");
+    std::unique_lock<std::mutex> la(cam->mu, std::defer_lock), lb(prev_cam->mu, std::defer_lock);
+    if (cam == prev_cam)
+        la.lock();
+    else
+        std::lock(la, lb);
+    try {
+        f();
+        return RT_OK;
+    } catch (const HipError& e) {
+        return set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        return set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_RENDER, e.what());
+    }
+}
+
+template <class T>
+static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
+    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
 extern "C" {
 
 int rt_version(void) { return RT_AMD_VERSION; }
@@ -1229,6 +1255,287 @@ int rt_camera_denoise_times(rt_camera* cam, int32_t* levels, float* guide_ms, fl
             if (l < L) hip_check(hipEventElapsedTime(&level_ms[l], ev[2 + l], ev[3 + l]), "hipEventElapsedTime");
         }
         hip_check(hipEventElapsedTime(total_ms, ev[0], ev[L + 3]), "hipEventElapsedTime");
+    });
+}
+
+// ---- Reprojection of a previous view's frame (reproject.hpp) -----------------------------------
+int rt_camera_get_view(const rt_camera* cam, rt_view* view) {
+    if (!cam || !view) return set_error(RT_ERR_INVALID, "null argument");
+    const RtCamera& C = cam->build.cam;
+    for (int k = 0; k < 3; ++k) {
+        view->center[k] = C.center[k];
+        view->pixel00[k] = C.pixel00[k];
+        view->du[k] = C.du[k];
+        view->dv[k] = C.dv[k];
+    }
+    view->width = C.width;
+    view->height = C.height;
+    return RT_OK;
+}
+
+int rt_camera_reusable_objects(const rt_camera* cam, uint8_t* out, int32_t capacity) {
+    if (!cam || !out) return set_error(RT_ERR_INVALID, "null argument");
+    const std::vector<uint8_t> t = cam->reusable_objects();
+    if ((int64_t)capacity < (int64_t)t.size())
+        return set_error(RT_ERR_INVALID, "rt_camera_reusable_objects: capacity below the number of objects");
+    if (!t.empty()) std::memcpy(out, t.data(), t.size());
+    return RT_OK;
+}
+
+// rt_reproject_options resolved: a zero field = the default.
+struct RpOpts {
+    float normal_min, sigma_plane, min_weight, nh;
+};
+static RpOpts rp_resolve(const rt_reproject_options* o, const std::string& who) {
+    RpOpts r = o ? RpOpts{o->normal_min, o->sigma_plane, o->min_weight, o->history_samples} : RpOpts{0.0f, 0.0f, 0.0f, 0.0f};
+    const std::pair<const char*, float> fields[] = {{"normal_min", r.normal_min},
+                                                    {"sigma_plane", r.sigma_plane},
+                                                    {"min_weight", r.min_weight},
+                                                    {"history_samples", r.nh}};
+    for (const auto& f : fields)
+        if (!(f.second >= 0.0f) || !std::isfinite(f.second))
+            throw std::invalid_argument(who + ": " + f.first + " must be positive and finite (0: the default)");
+    if (r.normal_min == 0.0f) r.normal_min = 0.9f;
+    if (r.sigma_plane == 0.0f) r.sigma_plane = 0.01f;
+    if (r.min_weight == 0.0f) r.min_weight = 0.25f;
+    if (r.nh == 0.0f) r.nh = 32.0f;
+    return r;
+}
+
+// The argument errors every reproject entry shares (host only).
+static void rp_check(const std::string& who, const float* prev_radiance, const float* radiance, int32_t samples,
+                     const float* radiance_out, const uint8_t* rgb_out) {
+    if (!prev_radiance) throw std::invalid_argument(who + ": prev_radiance is required");
+    if ((radiance_out || rgb_out) && !radiance)
+        throw std::invalid_argument(who + ": radiance_out and rgb_out need a fresh radiance to blend");
+    if (samples < 0) throw std::invalid_argument(who + ": samples must not be negative");
+}
+
+static void rp_same_scene(const rt_camera* a, const rt_camera* b) {
+    const SceneBuild &x = a->build, &y = b->build;
+    if (a != b && !(same_bytes(x.nodes, y.nodes) && same_bytes(x.prims, y.prims) && same_bytes(x.mats, y.mats) &&
+                    same_bytes(x.lights, y.lights) && same_bytes(x.prim_object, y.prim_object)))
+        throw std::invalid_argument("reproject: the cameras hold different scenes");
+}
+
+// The new view's side of a call: its guides, and the fresh frame and sample counts to blend
+// (null: history only) in one layout - row pitch `pitch` pixels, the region at (fx0, fy0).
+struct RpNew {
+    const float4 *gn, *gp;
+    const float* fresh;
+    const int32_t* pxs;
+    int pitch, fx0, fy0;
+    float m;
+};
+
+// The device side of a call once both views' guides and the previous radiance (pb.rad(),
+// region-packed) are there: the previous colour packed as the plain filter packs it, the gather,
+// then history -> nb.nrm(), weight -> nb.dist(), the blend -> nb.rad() / nb.u8. ev (or null):
+// events 2..4, recorded before and after the gather and after the unpack passes. Queued.
+static void rp_run(DnBufs& nb, DnBufs& pb, const RpView& view, const rt_region& r, const rt_region& pr,
+                   const uint8_t* d_reusable, int n_objects, const RpOpts& o, const RpNew& nw, bool want_hist,
+                   bool want_rad, bool want_u8, hipStream_t stream, hipEvent_t* ev) {
+    auto mark = [&](int k) {
+        if (ev) hip_check(hipEventRecord(ev[k], stream), "hipEventRecord");
+    };
+    hip_check(launch_denoise_pack(pb.rad(), pr.width, 0, 0, pr.width, pr.height, pb.gn, 1.0f, nullptr, pb.c0, pb.fn, stream),
+              "denoise_pack_kernel");
+    mark(2);
+    RpArgs a{};
+    a.view = view;
+    a.w = r.width, a.h = r.height;
+    a.px0 = pr.x, a.py0 = pr.y, a.pw = pr.width, a.ph = pr.height;
+    a.n_objects = n_objects;
+    a.normal_min = o.normal_min, a.sigma_plane = o.sigma_plane, a.min_weight = o.min_weight, a.nh = o.nh;
+    a.pitch = nw.pitch, a.fx0 = nw.fx0, a.fy0 = nw.fy0;
+    a.m = nw.m;
+    hip_check(launch_reproject(a, nw.gn, nw.gp, pb.gn, pb.gp, pb.c0, d_reusable, nw.fresh, nw.pxs, nb.c0,
+                               nw.fresh ? nb.c1.p : nullptr, stream),
+              "reproject_kernel");
+    mark(3);
+    const int n = r.width * r.height;
+    if (want_hist) hip_check(launch_denoise_unpack(nb.c0, n, nb.nrm(), nullptr, nb.dist(), stream), "denoise_unpack_kernel");
+    if (nw.fresh && (want_rad || want_u8))
+        hip_check(launch_denoise_unpack(nb.c1, n, want_rad ? nb.rad() : nullptr, want_u8 ? nb.u8.p : nullptr, nullptr, stream),
+                  "denoise_unpack_kernel");
+    mark(4);
+}
+
+int rt_reproject(int32_t width, int32_t height, const rt_region* region, const float* normal, const float* position,
+                 const float* distance, const int32_t* object, const rt_view* prev_view, const rt_region* prev_region,
+                 const float* prev_radiance, const float* prev_normal, const float* prev_position,
+                 const float* prev_distance, const int32_t* prev_object, const uint8_t* reusable, int32_t n_objects,
+                 const rt_reproject_options* options, const float* radiance, const int32_t* px_samples, int32_t samples,
+                 float* history_out, float* weight_out, float* radiance_out, uint8_t* rgb_out) {
+    const std::string who = "rt_reproject";
+    DnBufs nb, pb;
+    DevBuf<uint8_t> d_reusable;
+    int rc = RT_OK;
+    try {
+        if (width <= 0 || height <= 0) throw std::invalid_argument(who + ": width and height must be positive");
+        if (!normal || !position || !distance || !object)
+            throw std::invalid_argument(who + ": normal, position, distance and object are required");
+        if (!prev_view || !prev_normal || !prev_position || !prev_distance || !prev_object)
+            throw std::invalid_argument(who + ": prev_view, prev_normal, prev_position, prev_distance and prev_object are required");
+        if (prev_view->width <= 0 || prev_view->height <= 0)
+            throw std::invalid_argument(who + ": the previous view's width and height must be positive");
+        if (n_objects < 0 || (n_objects > 0 && !reusable))
+            throw std::invalid_argument(who + ": reusable must hold n_objects >= 0 entries");
+        rp_check(who, prev_radiance, radiance, samples, radiance_out, rgb_out);
+        const RpOpts o = rp_resolve(options, who);
+        const rt_region r = dn_region(region, width, height, who);
+        const rt_region pr = dn_region(prev_region, prev_view->width, prev_view->height, who);
+        const RpView view = rp_view_constants(prev_view->center, prev_view->pixel00, prev_view->du, prev_view->dv,
+                                              prev_view->width, prev_view->height);
+        const hipStream_t stream = nullptr;
+        const int n = r.width * r.height, np = pr.width * pr.height;
+        nb.ensure((size_t)n);
+        pb.ensure((size_t)np);
+        d_reusable.ensure((size_t)std::max(n_objects, 1), "hipMalloc(reusable objects)");
+        if (n_objects > 0)
+            hip_check(hipMemcpyAsync(d_reusable, reusable, (size_t)n_objects, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+        dn_upload(nb.nrm(), normal, 3 * sizeof(float), width, r, stream);
+        dn_upload(nb.pos(), position, 3 * sizeof(float), width, r, stream);
+        dn_upload(nb.dist(), distance, sizeof(float), width, r, stream);
+        dn_upload(nb.obj, object, sizeof(int32_t), width, r, stream);
+        hip_check(launch_guides_pack(DenoiseGuides{nb.gn, nb.gp}, n, nb.nrm(), nb.pos(), nb.dist(), nb.obj, stream),
+                  "guides_pack_kernel");
+        dn_upload(pb.nrm(), prev_normal, 3 * sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.pos(), prev_position, 3 * sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.dist(), prev_distance, sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.obj, prev_object, sizeof(int32_t), prev_view->width, pr, stream);
+        hip_check(launch_guides_pack(DenoiseGuides{pb.gn, pb.gp}, np, pb.nrm(), pb.pos(), pb.dist(), pb.obj, stream),
+                  "guides_pack_kernel");
+        dn_upload(pb.rad(), prev_radiance, 3 * sizeof(float), prev_view->width, pr, stream);
+        // (the guides are packed: the staging arrays now carry the fresh frame and the counts)
+        if (radiance) dn_upload(nb.rad(), radiance, 3 * sizeof(float), width, r, stream);
+        if (radiance && px_samples) dn_upload(nb.obj, px_samples, sizeof(int32_t), width, r, stream);
+        const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
+                       r.width, 0, 0, (float)samples};
+        rp_run(nb, pb, view, r, pr, d_reusable, n_objects, o, nw, history_out || weight_out, radiance_out != nullptr,
+               rgb_out != nullptr, stream, nullptr);
+        dn_download(history_out, nb.nrm(), 3 * sizeof(float), width, r, stream);
+        dn_download(weight_out, nb.dist(), sizeof(float), width, r, stream);
+        dn_download(radiance_out, nb.rad(), 3 * sizeof(float), width, r, stream);
+        dn_download(rgb_out, nb.u8, 3, width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    } catch (const HipError& e) {
+        rc = set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        rc = set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        rc = set_error(RT_ERR_RENDER, e.what());
+    }
+    nb.free();
+    pb.free();
+    d_reusable.reset();
+    return rc;
+}
+
+// The previous view's side of a camera call, on the current device: its context with the
+// radiance uploaded into rp_prev.rad() and the guide pass queued into rp_prev.gn / gp.
+static DnBufs& rp_prev_side(rt_camera* prev_cam, const rt_region& pr, const float* prev_radiance, hipStream_t stream,
+                            hipEvent_t* ev, const std::function<void()>& new_guides) {
+    DevCtx& p = prev_cam->current();
+    p.ensure_device();
+    DnBufs& pb = p.rp_prev;
+    pb.ensure((size_t)pr.width * pr.height);
+    dn_upload(pb.rad(), prev_radiance, 3 * sizeof(float), prev_cam->build.cam.width, pr, stream);
+    hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+    new_guides();
+    p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{pb.gn, pb.gp}, stream);
+    hip_check(hipEventRecord(ev[1], stream), "hipEventRecord");
+    return pb;
+}
+
+static RpView rp_camera_view(const rt_camera* cam) {
+    const RtCamera& C = cam->build.cam;
+    return rp_view_constants(C.center, C.pixel00, C.du, C.dv, C.width, C.height);
+}
+
+int rt_camera_reproject(rt_camera* cam, const rt_region* region, rt_camera* prev_cam, const rt_region* prev_region,
+                        const rt_reproject_options* options, const float* prev_radiance, const float* radiance,
+                        const int32_t* px_samples, int32_t samples, float* history_out, float* weight_out,
+                        float* radiance_out, uint8_t* rgb_out) {
+    return two_camera_call(cam, prev_cam, [&] {
+        const std::string who = "rt_camera_reproject";
+        const RtCamera &C = cam->build.cam, &PC = prev_cam->build.cam;
+        rp_check(who, prev_radiance, radiance, samples, radiance_out, rgb_out);
+        const RpOpts o = rp_resolve(options, who);
+        const rt_region r = dn_region(region, C.width, C.height, who);
+        const rt_region pr = dn_region(prev_region, PC.width, PC.height, who);
+        rp_same_scene(cam, prev_cam);
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        const hipStream_t stream = nullptr;
+        DnBufs& nb = c.dn;
+        nb.ensure((size_t)r.width * r.height);
+        hipEvent_t* ev = c.rp_events();
+        const uint8_t* d_reusable = c.ensure_reusable();
+        if (radiance) dn_upload(nb.rad(), radiance, 3 * sizeof(float), C.width, r, stream);
+        if (radiance && px_samples) dn_upload(nb.obj, px_samples, sizeof(int32_t), C.width, r, stream);
+        DnBufs& pb = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] {
+            c.launch_guide_pass(r, cam->traversal, DenoiseGuides{nb.gn, nb.gp}, stream);
+        });
+        const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
+                       r.width, 0, 0, (float)samples};
+        rp_run(nb, pb, rp_camera_view(prev_cam), r, pr, d_reusable, C.n_prims, o, nw, history_out || weight_out,
+               radiance_out != nullptr, rgb_out != nullptr, stream, ev);
+        c.rp_timed = true;
+        dn_download(history_out, nb.nrm(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(weight_out, nb.dist(), sizeof(float), C.width, r, stream);
+        dn_download(radiance_out, nb.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(rgb_out, nb.u8, 3, C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_progressive_reproject(rt_camera* cam, rt_camera* prev_cam, const rt_region* prev_region,
+                                    const rt_reproject_options* options, const float* prev_radiance, uint8_t* rgb,
+                                    float* radiance, float* weight_out) {
+    return two_camera_call(cam, prev_cam, [&] {
+        const std::string who = "rt_camera_progressive_reproject";
+        (void)cam->session(who.c_str());
+        session_radiance(cam, who);
+        rp_check(who, prev_radiance, nullptr, 0, nullptr, nullptr);
+        const RpOpts o = rp_resolve(options, who);
+        const RtCamera &C = cam->build.cam, &PC = prev_cam->build.cam;
+        const rt_region pr = dn_region(prev_region, PC.width, PC.height, who);
+        rp_same_scene(cam, prev_cam);
+        DevCtx& c = session_with(cam, who, 0);
+        DevCtx::ProgSession& P = c.prog;
+        const rt_region r = P.region;
+        const hipStream_t stream = nullptr;
+        DnBufs& nb = c.dn;
+        nb.ensure((size_t)r.width * r.height);
+        hipEvent_t* ev = c.rp_events();
+        const uint8_t* d_reusable = c.ensure_reusable();
+        DnBufs& pb = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] { session_guides(cam, c, stream); });
+        const RpNew nw{P.d_gn, P.d_gp, P.d_rad, P.d_pxs, C.width, r.x, r.y, 0.0f};
+        rp_run(nb, pb, rp_camera_view(prev_cam), r, pr, d_reusable, C.n_prims, o, nw, weight_out != nullptr,
+               radiance != nullptr, rgb != nullptr, stream, ev);
+        c.rp_timed = true;
+        dn_download(weight_out, nb.dist(), sizeof(float), C.width, r, stream);
+        dn_download(radiance, nb.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(rgb, nb.u8, 3, C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_reproject_times(rt_camera* cam, float* guide_ms, float* reproject_ms, float* total_ms) {
+    if (!guide_ms || !reproject_ms || !total_ms) return set_error(RT_ERR_INVALID, "null argument");
+    return camera_call(cam, [&] {
+        DevCtx* c = nullptr;
+        for (auto& x : cam->ctxs)
+            if (x->rp_timed) c = x.get();
+        if (!c) throw std::invalid_argument("rt_camera_reproject_times: no reproject call yet");
+        DeviceScope scope;
+        hip_check(hipSetDevice(c->device), "hipSetDevice");
+        hipEvent_t* ev = c->rp_ev.data();  // guide passes [0, 1), pack [1, 2), gather [2, 3), unpack [3, 4)
+        hip_check(hipEventSynchronize(ev[4]), "hipEventSynchronize");
+        hip_check(hipEventElapsedTime(guide_ms, ev[0], ev[1]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(reproject_ms, ev[2], ev[3]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(total_ms, ev[0], ev[4]), "hipEventElapsedTime");
     });
 }
 

@@ -51,6 +51,9 @@ _UNITS = [
     # (no contraction; plain / and sqrtf are IEEE under hipcc's defaults) - the output equals
     # tests/denoise_ref.py and tests/denoise_var_ref.py in every bit
     ("denoise.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the reprojection gather: as the filter, every fp32 operation rounds once - the output equals
+    # tests/reproject_ref.py in every bit
+    ("reproject.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the primary-ray candidate table's builder: the kernel and the host loop run the same double
     # operations, one rounding each, so the two tables are equal in every bit
     ("primary.hip", ["-ffp-contract=off"], True),
@@ -68,7 +71,7 @@ _UNITS = [
     ("image.cpp", [], False),
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "reproject.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp"]
 _LIBS = ["-lz"]
 

@@ -101,6 +101,16 @@ class RtDenoiseVarOptions(C.Structure):
 DENOISE_MAX_LEVELS = 8
 
 
+class RtView(C.Structure):
+    _fields_ = [("center", C.c_float * 3), ("pixel00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class RtReprojectOptions(C.Structure):
+    _fields_ = [("normal_min", C.c_float), ("sigma_plane", C.c_float), ("min_weight", C.c_float),
+                ("history_samples", C.c_float)]
+
+
 class RtPrimaryInfo(C.Structure):
     _fields_ = [("available", C.c_int32), ("used", C.c_int32), ("built", C.c_int32), ("min_samples", C.c_int32),
                 ("build_ms", C.c_float)]
@@ -218,6 +228,20 @@ _SIGS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_camera_progressive_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseVarOptions), C.c_void_p,
                                                          C.c_void_p, C.c_void_p]),
+    "rt_camera_get_view": (C.c_int, [C.c_void_p, C.POINTER(RtView)]),
+    "rt_camera_reusable_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "rt_reproject": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.POINTER(RtView), C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RtReprojectOptions),
+                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_reproject": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.c_void_p, C.POINTER(RtRegion),
+                                      C.POINTER(RtReprojectOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_progressive_reproject": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtRegion),
+                                                  C.POINTER(RtReprojectOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "rt_camera_reproject_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -174,6 +174,87 @@ def denoise(radiance, normal, position, distance, object, region=None, *, levels
     return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
 
 
+def _reproject_options(normal_min, sigma_plane, min_weight, history_samples) -> _lib.RtReprojectOptions:
+    """rt_reproject_options (a zero field = the default; the library validates the rest)."""
+    return _lib.RtReprojectOptions(float(normal_min), float(sigma_plane), float(min_weight), float(history_samples))
+
+
+def _out_array(a, dtype, shape, what: str):
+    """Pointer of an optional caller-owned output array of `shape` (any shape of that size)."""
+    import numpy as np
+    if a is None:
+        return None
+    if (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]
+            or a.size != int(np.prod(shape))):
+        raise ValueError(f"{what} must be a writable C-contiguous {np.dtype(dtype).name} array of "
+                         f"{'x'.join(str(v) for v in shape)} values")
+    return a.ctypes.data
+
+
+def _reproject_frames(H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out):
+    """The new frame's side of a reproject call: (fresh radiance or None, its pointer, px_samples
+    pointer, scalar samples, blend array, its pointer, rgb pointer, history array, its pointer,
+    weight pointer, keep-alive). Without `radiance` there is no blend: out / rgb raise."""
+    import numpy as np
+    if radiance is None and (out is not None or rgb is not None or px_samples is not None):
+        raise ValueError("out, rgb and px_samples need radiance=")
+    rad = None if radiance is None else _f32_frame(radiance, (H, W, 3), "radiance")
+    pxs = None if px_samples is None else np.ascontiguousarray(px_samples, dtype=np.int32)
+    if pxs is not None and pxs.size != H * W:
+        raise ValueError(f"px_samples must hold {H}x{W} values, not {pxs.size}")
+    res = None if rad is None else _denoise_out(rad, out)
+    hist = np.zeros((H, W, 3), np.float32) if history_out is None and rad is None else history_out
+    uptr, keep = _host_ptr(rgb, H * W * 3, "rgb")
+    return (rad, None if rad is None else rad.ctypes.data, None if pxs is None else pxs.ctypes.data,
+            0 if samples is None else int(samples), res, None if res is None else res.ctypes.data, uptr, hist,
+            _out_array(hist, np.float32, (H, W, 3), "history_out"),
+            _out_array(weight_out, np.float32, (H, W), "weight_out"), (pxs, keep))
+
+
+def reproject(prev_radiance, prev_view, prev_guides, *, normal, position, distance, object, reusable, region=None,
+              prev_region=None, radiance=None, px_samples=None, samples=None, rgb=None, out=None, history_out=None,
+              weight_out=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0):
+    """rt_reproject: a previous view's frame reprojected into a new view, explicit buffers, no
+    camera. prev_radiance float32 (Hp, Wp, 3), prev_view as Camera.view() and prev_guides as
+    Camera.render_guides() of the previous camera; normal / position / distance / object: the new
+    view's guides (pass **cam.render_guides()); reusable: uint8 per object, as
+    Camera.reusable_objects(). With a fresh `radiance` (float32 (H, W, 3)) and its sample counts
+    (`px_samples` int32 (H, W), or one scalar `samples`) returns the blend (H, W, 3) - a new array,
+    or `out` - and `rgb` (optional u8 H*W*3) receives its u8; without, returns the history.
+    `history_out` (float32 (H, W, 3)) and `weight_out` (float32 (H, W)) are optional; only the
+    region is written. Equals tests/reproject_ref.py in every bit."""
+    import numpy as np
+    obj = np.asarray(object)
+    if obj.ndim != 2:
+        raise ValueError("object must have shape (H, W)")
+    H, W = obj.shape
+    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
+    view = _lib.RtView()
+    for k in ("center", "pixel00", "du", "dv"):
+        getattr(view, k)[:] = [float(v) for v in np.asarray(prev_view[k], dtype=np.float32)]
+    view.width, view.height = Wp, Hp
+    g = [_f32_frame(normal, (H, W, 3), "normal"), _f32_frame(position, (H, W, 3), "position"),
+         _f32_frame(distance, (H, W), "distance"), _f32_frame(obj, (H, W), "object")]
+    pg = [_f32_frame(prev_guides["normal"], (Hp, Wp, 3), "normal"),
+          _f32_frame(prev_guides["position"], (Hp, Wp, 3), "position"),
+          _f32_frame(prev_guides["distance"], (Hp, Wp), "distance"),
+          _f32_frame(prev_guides["object"], (Hp, Wp), "object")]
+    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
+    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
+    rad, radp, pxsp, ns, res, resp, uptr, hist, histp, wptr, _keep = _reproject_frames(
+        H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
+    reg = None if region is None else _region(region)
+    preg = None if prev_region is None else _region(prev_region)
+    opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+    _lib.check(_lib.load().rt_reproject(
+        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], C.byref(view),
+        C.byref(preg) if preg is not None else None, prad.ctypes.data, *[a.ctypes.data for a in pg],
+        reus.ctypes.data if reus.size else None, int(reus.size), C.byref(opts), radp, pxsp, ns, histp, wptr, resp, uptr))
+    if res is None:
+        return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
+    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+
 class Camera:
     """The reference Camera (src/camera.ts:61-472), rendering on MI355X."""
 
@@ -460,6 +541,59 @@ class Camera:
         return {"levels": int(n.value), "guide_ms": float(g.value), "level_ms": [float(v) for v in lv][:n.value],
                 "total_ms": float(t.value)}
 
+    # -- reprojection of a previous view's frame -------------------------------------
+    def view(self) -> dict:
+        """The camera's view (rt_camera_get_view): {"center", "pixel00", "du", "dv": float32 (3,),
+        "width", "height"} - the fp32 vectors the guide pass builds its rays from."""
+        import numpy as np
+        v = _lib.RtView()
+        _lib.check(self._lib.rt_camera_get_view(self._h, C.byref(v)))
+        d = {k: np.array(list(getattr(v, k)), dtype=np.float32) for k in ("center", "pixel00", "du", "dv")}
+        d.update(width=int(v.width), height=int(v.height))
+        return d
+
+    def reusable_objects(self):
+        """rt_camera_reusable_objects: uint8 per SceneData.objects entry, 1 where the object's
+        resolved material is lambert or light - the surfaces whose radiance another view may reuse."""
+        import numpy as np
+        out = np.zeros(max(self._info.n_objects, 1), np.uint8)
+        _lib.check(self._lib.rt_camera_reusable_objects(self._h, out.ctypes.data, int(out.size)))
+        return out[:self._info.n_objects]
+
+    def reproject(self, prev_cam: "Camera", prev_radiance, region=None, prev_region=None, radiance=None,
+                  px_samples=None, samples=None, rgb=None, out=None, history_out=None, weight_out=None, *,
+                  normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0):
+        """rt_camera_reproject: `prev_radiance` (float32 (Hp, Wp, 3), a frame of `prev_cam`, a camera
+        of the same scene) reprojected into this camera's view; both views' guides are computed on
+        the device. With a fresh `radiance` of this camera and its sample counts (`px_samples`
+        int32 (H, W), or one scalar `samples`) returns the blend (H, W, 3) - a new array, or `out` -
+        and `rgb` receives its u8; without, returns the history. `history_out` / `weight_out` are
+        optional float32 arrays; only the region is written. Equals reproject(prev_radiance,
+        prev_cam.view(), prev_cam.render_guides(), reusable=self.reusable_objects(),
+        **self.render_guides(), ...). The result can be fed to denoise() and chained as the next
+        call's prev_radiance."""
+        H, W = self.image_height, self.image_width
+        Hp, Wp = prev_cam.image_height, prev_cam.image_width
+        prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
+        rad, radp, pxsp, ns, res, resp, uptr, hist, histp, wptr, _keep = _reproject_frames(
+            H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
+        reg = None if region is None else _region(region)
+        preg = None if prev_region is None else _region(prev_region)
+        opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+        _lib.check(self._lib.rt_camera_reproject(self._h, C.byref(reg) if reg is not None else None, prev_cam._h,
+                                                 C.byref(preg) if preg is not None else None, C.byref(opts),
+                                                 prad.ctypes.data, radp, pxsp, ns, histp, wptr, resp, uptr))
+        if res is None:
+            return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
+        return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+    def reproject_times(self) -> dict:
+        """Device time of the last reproject / ProgressiveRender.reprojected call, from HIP events
+        (rt_camera_reproject_times): the guide passes, the gather kernel and the whole span."""
+        g, r, t = C.c_float(), C.c_float(), C.c_float()
+        _lib.check(self._lib.rt_camera_reproject_times(self._h, C.byref(g), C.byref(r), C.byref(t)))
+        return {"guide_ms": float(g.value), "reproject_ms": float(r.value), "total_ms": float(t.value)}
+
     def release_device(self) -> None:
         """Free the device copies; the next render re-creates them (rt_camera_release_device)."""
         _lib.check(self._lib.rt_camera_release_device(self._h))
@@ -579,6 +713,35 @@ class ProgressiveRender:
         else:
             _lib.check(cam._lib.rt_camera_progressive_denoise(cam._h, C.byref(opts), ptr, rptr))
         shape = (cam.image_height, cam.image_width, 3)
+        if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
+            return radiance.reshape(shape)
+        return radiance
+
+    def reprojected(self, prev_cam: Camera, prev_radiance, rgb=None, radiance=None, weight_out=None, *,
+                    prev_region=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0):
+        """The session's frame as it stands after the last step, blended with `prev_radiance`
+        (float32 (Hp, Wp, 3), a frame of `prev_cam`, a camera of the same scene) reprojected into
+        this view, every pixel weighted by its own sample count (rt_camera_progressive_reproject):
+        only the previous radiance is uploaded, and the session itself is not touched. `rgb` (u8
+        W*H*3), `radiance` (float32 W*H*3) and `weight_out` (float32 (H, W)) are optional
+        caller-owned full-frame buffers; only the region is written. Returns the blend as a
+        (H, W, 3) array (`radiance` when given; else a new one, zero outside the region)."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        import numpy as np
+        cam = self._cam
+        shape = (cam.image_height, cam.image_width, 3)
+        if radiance is None:
+            radiance = np.zeros(shape, np.float32)
+        prad = _f32_frame(prev_radiance, (prev_cam.image_height, prev_cam.image_width, 3), "prev_radiance")
+        ptr, _k0 = _host_ptr(rgb, cam.byte_length, "rgb")
+        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
+        wptr = _out_array(weight_out, np.float32, shape[:2], "weight_out")
+        preg = None if prev_region is None else _region(prev_region)
+        opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+        _lib.check(cam._lib.rt_camera_progressive_reproject(cam._h, prev_cam._h,
+                                                            C.byref(preg) if preg is not None else None,
+                                                            C.byref(opts), prad.ctypes.data, ptr, rptr, wptr))
         if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
             return radiance.reshape(shape)
         return radiance
