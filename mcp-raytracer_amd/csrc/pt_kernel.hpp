@@ -2823,20 +2823,29 @@ __global__ __launch_bounds__(kBlockChunk) void pt_chunk_kernel(DevScene S0, RtRe
 // ---------------------------------------------------------------------------
 // Stage-compacted pool kernel (fixed spp, no emission stack): the chunked
 // kernel's work items and per-sample records, but lanes are not tied to paths.
-// Each wave keeps kPoolK path slots in LDS and two queues of slot indices:
-//   A (trace): start the sample's path (getRay) or continue it, depth cut-off /
-//     roulette, closest hit, miss or hit record + material scatter;
-//   D (diffuse): the mixture-PDF light sampling, its value and the throughput
-//     update (src/camera.ts:263-315), which about half of the hits need.
-// Every trip runs ONE stage on up to 64 queued paths (ballot/mbcnt queue
-// appends): D once 64 paths wait (or when it is the longer queue), A
-// otherwise. So the diffuse shading runs on full waves rather than on the
-// lanes whose path happens to need it in a given trip (the north star's
-// persistent-wavefront work queues). D is split by the mixture's branch
-// by branch: A draws the mixture uniform ahead (on a copy of the path's
-// RNG state; D draws the same value again) and queues the path for the
-// cosine-PDF or the light-PDF generate, so a D trip runs one of the two
-// sampling branches instead of both at half the lanes. Each path's arithmetic
+// Each wave keeps kPoolK path slots in LDS and four stacks of slot indices:
+// `an` (samples whose path is to start), `d` / `dl` (diffuse hits waiting for the
+// cosine-PDF / light-PDF generate) and `ac` (paths continuing after a specular
+// scatter). A trip pops up to 64 slots and runs one FRONT stage, chosen for the
+// whole wave, then the BACK stage that every path shares:
+//   front N: pops `an` - the item hand-out and the path start (getRay);
+//   front Dc / Dl: pops `d` / `dl` - the mixture-PDF light sampling, its value and
+//     the throughput update (src/camera.ts:263-315) of one sampling branch; the
+//     bounce's new ray stays in registers. Free lanes are filled from `ac`; they idle
+//     through the front;
+//   no front: pops `ac` alone - only from a full wave or when no other stack has work
+//     (the drain at a launch's end), so specular paths never park slots;
+//   back: depth cut-off / roulette, closest hit (after N with the primary-ray table:
+//     the table's candidates), miss or hit record + material scatter. The path's sample
+//     is recorded, or it continues specularly (`ac`), or its diffuse hit is queued by the
+//     mixture's branch: the back draws the mixture uniform ahead (on a copy of the path's
+//     RNG state; D draws the same value again), so a D front runs one of the two sampling
+//     branches instead of both at half the lanes.
+// One slot-store block and one group of ballot/mbcnt queue appends end a trip: a diffuse
+// bounce passes through the slot once (hit -> D), not twice (2.6 trips per 64 samples
+// where a trace stage and a diffuse stage of their own took 4.1). The diffuse shading
+// still runs on full waves rather than on the lanes whose path happens to need it in a
+// given trip (the north star's persistent-wavefront work queues). Each path's arithmetic
 // and draw order are path_trip's, so every sample record - and the image - is
 // bit-identical.
 // ---------------------------------------------------------------------------
@@ -2906,8 +2915,9 @@ __device__ __forceinline__ const uint2* primary_table_opaque() {
 
 // The pool kernel's body, shared by its two entries. PRIM: the trips that start new paths
 // take each primary ray's candidates from the primary-ray table (primary.hpp) instead
-// of running the fp32 pre-filter pass: a trip serves one of the two A stacks, so it is
-// wave-uniformly all primary rays or none, and the branch costs no divergence.
+// of running the fp32 pre-filter pass: an N trip pops only the `an` stack (no `ac` lanes
+// ride in it), so a trip is wave-uniformly all primary rays or none, and the branch costs
+// no divergence.
 template <class Real, int TRAV, int LDSS, bool PRIM>
 // (The arguments by value, as the entries take them: by reference the compiler kept them in the
 // kernarg segment and the LDS-resident ref kernel went from 53 to 76 spilled SGPRs.)
@@ -2939,10 +2949,10 @@ __device__ __forceinline__ void pool_trips(DevScene S0, RtRegion reg, RenderOut 
         qa[k] = (uint8_t)k;
         G[k] = make_float4(0.f, 0.f, pool_meta(PH_ITEM, 0, 0), 0.f);
     }
-    int a_cnt = kPoolK, d_cnt = 0;  // wave-uniform queue state
-    int dl_cnt = 0;  // the D queue's light-branch stack (d_cnt: cosine-branch stack)
-    // the A queue as two stacks in qa: paths to start from the bottom (an_cnt),
-    // paths in flight from the top (ac_cnt); a_cnt stays their sum
+    // wave-uniform queue state. qd: the cosine-branch stack from the bottom (d_cnt), the
+    // light-branch stack from the top (dl_cnt). qa: paths to start from the bottom (an_cnt),
+    // paths continuing after a specular scatter from the top (ac_cnt).
+    int d_cnt = 0, dl_cnt = 0;
     int an_cnt = kPoolK, ac_cnt = 0;
     int pool_next, pool_end;  // wave-uniform item hand-out
     bool exhausted;
@@ -2960,76 +2970,61 @@ __device__ __forceinline__ void pool_trips(DevScene S0, RtRegion reg, RenderOut 
         return s < s_end ? PH_NEW : PH_ITEM;
     };
 
-    while (a_cnt + d_cnt + dl_cnt > 0) {
+    enum : int { FR_N, FR_D, FR_NONE };  // a trip's front stage
+    while (an_cnt + ac_cnt + d_cnt + dl_cnt > 0) {
         // other lanes' slot and queue writes of the previous trip (one wave: LDS is in order)
         __asm__ volatile("" ::: "memory");
         prof_trip<PP>(pf);
         psec<PP>(pf, PR_ACC);  // the previous trip's records, slot stores and queue appends
+        // ---- the front's choice: a stack that fills the wave (D, ac, N in that order), else the
+        // longer D stack, else N; ac alone only as a full wave or when nothing else has work ----
         const bool dtop = dl_cnt > d_cnt;  // the longer D stack
         const int dn = dtop ? dl_cnt : d_cnt;
-        const bool atop = ac_cnt > an_cnt;  // the longer A stack
-        const int an = atop ? ac_cnt : an_cnt;
-        if (dn >= kWave || dn > an) {
-            // ---- D: diffuse shading of up to 64 queued paths ----
-            const int n = min(kWave, dn);
-            int k = -1, phase = 0;
-            if (lane < n) k = (int)qd[dtop ? kPoolK - dl_cnt + lane : d_cnt - n + lane];
-            if (dtop) dl_cnt -= n;
-            else d_cnt -= n;
-            if (k >= 0) {
-                const float4 g0 = G[k], g1 = G[kPoolK + k], g2 = G[2 * kPoolK + k];
-                const float2 g3 = G3[k];
-                Path<false> P;
-                P.rng = (uint64_t)__float_as_uint(g0.x) | ((uint64_t)__float_as_uint(g0.y) << 32);
-                P.bounces = meta_phase(g0.z);
-                P.em_n = 0;
-                P.o = V3{g1.x, g1.y, g1.z};
-                P.d = V3{g2.x, g2.y, g2.z};
-                P.T = V3{g2.w, g3.x, g3.y};
-                const int hf = hs_hf(g0.w);
-                const int h = hf & 0x3fff;
-                const bool planar = (hf >> 14) & 1, front = (hf >> 15) & 1;
-                const V3 att = ld3(S.mats[meta_mat(g0.z)].color);  // the Lambertian scatter's attenuation
-                const int clog2 = meta_clog2(g0.z), slot = __float_as_int(g1.w);
-                int s = hs_s(g0.w);
-                const int s_end = item_end(s, clog2);
-                phase = P.bounces;
-                const RtCamera& C = cam_opaque();
-                const bool dterm =
-                    dtop ? shade_diffuse<Real, false, false, PP, 2>(S, C, P, h, planar, front, P.o, P.d, att, cnt, pf)
-                         : shade_diffuse<Real, false, false, PP, 1>(S, C, P, h, planar, front, P.o, P.d, att, cnt, pf);
-                if (dterm) {
-                    // mixture value cut-off: the level's emission (as computed at the hit: T is unchanged)
-                    const V3 c = mulv(ld3(S.mats[S.prims[h].mat].emitted), P.T);
-                    phase = record(c, P.bounces, slot, s, s_end);
-                }
-                G[k] = make_float4(__uint_as_float((uint32_t)P.rng), __uint_as_float((uint32_t)(P.rng >> 32)),
-                                   pool_meta(phase, clog2, 0), pool_hs(0, s));
-                G[2 * kPoolK + k] = make_float4(P.d.x, P.d.y, P.d.z, P.T.x);
-                G3[k] = make_float2(P.T.y, P.T.z);
-            }
-            stack_push(qa, false, an_cnt, k >= 0 && phase < 0, k);
-            stack_push(qa, true, ac_cnt, k >= 0 && phase >= 0, k);
-            a_cnt = an_cnt + ac_cnt;
+        const int fr = dn >= kWave       ? FR_D
+                       : ac_cnt >= kWave ? FR_NONE
+                       : an_cnt >= kWave ? FR_N
+                       : dn > 0          ? FR_D
+                       : an_cnt > 0      ? FR_N
+                                         : FR_NONE;
+        int k = -1;
+        int nd = 0;  // FR_D: the lanes that shade a diffuse bounce (the rest ride from ac)
+        if (fr == FR_D) {
+            nd = min(kWave, dn);
+            const int na = min(kWave - nd, ac_cnt);
+            if (lane < nd) k = (int)qd[dtop ? kPoolK - dl_cnt + lane : d_cnt - nd + lane];
+            else if (lane < nd + na) k = (int)qa[kPoolK - ac_cnt + lane - nd];
+            if (dtop) dl_cnt -= nd;
+            else d_cnt -= nd;
+            ac_cnt -= na;
+        } else if (fr == FR_N) {
+            const int n = min(kWave, an_cnt);
+            if (lane < n) k = (int)qa[an_cnt - n + lane];
+            an_cnt -= n;
         } else {
-            // ---- A: trace up to 64 queued paths ----
-            const int n = min(kWave, an);
-            int k = -1;
-            if (lane < n) k = (int)qa[atop ? kPoolK - ac_cnt + lane : an_cnt - n + lane];
-            if (atop) ac_cnt -= n;
-            else an_cnt -= n;
-            a_cnt -= n;
-            float4 g0 = make_float4(0.f, 0.f, pool_meta(PH_ITEM, 0, 0), 0.f), g1 = g0, g2 = g0;
-            float2 g3 = make_float2(0.f, 0.f);
-            if (k >= 0) {
-                g0 = G[k];
-                g1 = G[kPoolK + k];
-                g2 = G[2 * kPoolK + k];
-                g3 = G3[k];
-            }
-            int phase = meta_phase(g0.z), clog2 = meta_clog2(g0.z), slot = __float_as_int(g1.w);
-            int s = hs_s(g0.w);
-            // work items for slots without one (the chunked kernel's guided hand-out)
+            const int n = min(kWave, ac_cnt);
+            if (lane < n) k = (int)qa[kPoolK - ac_cnt + lane];
+            ac_cnt -= n;
+        }
+        float4 g0 = make_float4(0.f, 0.f, pool_meta(PH_ITEM, 0, 0), 0.f), g1 = g0, g2 = g0;
+        float2 g3 = make_float2(0.f, 0.f);
+        if (k >= 0) {
+            g0 = G[k];
+            g1 = G[kPoolK + k];
+            g2 = G[2 * kPoolK + k];
+            g3 = G3[k];
+        }
+        int phase = meta_phase(g0.z), clog2 = meta_clog2(g0.z), slot = __float_as_int(g1.w);
+        int s = hs_s(g0.w);
+        const RtCamera& C = cam_opaque();
+        Path<false> P;
+        bool keep = k >= 0;
+        bool path = false;  // the lane holds a path in this trip
+        bool term = false;  // ... which ends in it: `c` is the sample's radiance
+        V3 c = v3(0, 0, 0);
+        uint2 prec = make_uint2(0u, 0u);  // PRIM: the pixel's record of the primary-ray table
+        if (fr == FR_N) {
+            // ---- N: work items for slots without one (the chunked kernel's guided hand-out),
+            // then the path starts ----
             const unsigned long long need = __ballot(k >= 0 && phase == PH_ITEM);
             if (need != 0ull && !exhausted) {
                 if (pool_next >= pool_end) take_pool(out, sb, lane, pool_next, pool_end, exhausted);
@@ -3050,103 +3045,126 @@ __device__ __forceinline__ void pool_trips(DevScene S0, RtRegion reg, RenderOut 
                     pool_next += take;
                 }
             }
-            const bool keep = k >= 0 && (phase != PH_ITEM || !exhausted);  // drained slots leave the pool
-            bool to_d = false, d_light = false;
-            if (k >= 0 && phase != PH_ITEM) {
-                const RtCamera& C = cam_opaque();
-                Path<false> P;
-                uint2 prec = make_uint2(0u, 0u);  // PRIM: the pixel's record of the primary-ray table
-                if (phase == PH_NEW) {
-                    int i, j;  // the slot's pixel (the hand-out's slot_pixel)
-                    slot_pixel(sb, reg, tiles_x, rtx, endX, endY, slot, i, j);
-                    const uint32_t pix = (uint32_t)j * (uint32_t)C.width + (uint32_t)i;
-                    if (PRIM) prec = primary_table_opaque()[pix];  // in flight during the path start
-                    path_begin<Real, false>(C, P, pixel_center<Real>(C, i, j), pix, (uint32_t)(sb.s_base + s));
-                    // Wait for the record here, inside the block that issued its load (slot_pixel's
-                    // note): pending on the paths around this block, its registers would make later
-                    // writes of them wait with vmcnt(0), for the sample records stored before them too.
-                    // This is the trip loop's one vector-memory load; on gfx9 the wait also covers the
-                    // previous trip's record stores, which the path start has given time to drain.
-                    if (PRIM) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (gfx9 encoding)
-                } else {
-                    P.rng = (uint64_t)__float_as_uint(g0.x) | ((uint64_t)__float_as_uint(g0.y) << 32);
-                    P.o = V3{g1.x, g1.y, g1.z};
-                    P.d = V3{g2.x, g2.y, g2.z};
-                    P.T = V3{g2.w, g3.x, g3.y};
-                    P.bounces = phase;
-                    P.em_n = 0;
-                }
-                V3 c;
-                psec<PP>(pf, PR_NEWPATH);  // item hand-out and path starts
-                bool term = path_pre<Real, false, PP>(C, P, pf, c);
-                V3 att;
-                int hf = 0, dmat = 0;
-                unsigned long long err = 0ull;  // this sample's error flags (its miss)
-                if (!term) {
-                    const RayK<Real> ray = make_ray<Real>(P.o, P.d);
-                    Real t;
-                    int h;
-                    if (PRIM && !atop) {  // the new-path stack: every lane traces a primary ray
-                        psec<PP>(pf, PR_TILE);  // (no pre-filter section)
-                        h = closest_hit_primary<Real, false>(S, ray, t, prec, cnt);
-                    } else if (PP && TRAV == TRAV_BRUTE && C.n_prims <= kBruteMaxPrims)  // section timer
-                        h = closest_hit_brute_nf<Real, false>(S, C.n_prims, ray, t, lot_column(stk), cnt,
-                                                              [&]() { psec<PP>(pf, PR_TILE); });
-                    else
-                        h = closest_hit_any<Real, false, TRAV>(S, C.n_prims, ray, t, stk, cnt);
-                    psec<PP>(pf, PR_HIT);
-                    if (h < 0) {
+            keep = k >= 0 && (phase != PH_ITEM || !exhausted);  // drained slots leave the pool
+            if (k >= 0 && phase == PH_NEW) {
+                path = true;
+                int i, j;  // the slot's pixel (the hand-out's slot_pixel)
+                slot_pixel(sb, reg, tiles_x, rtx, endX, endY, slot, i, j);
+                const uint32_t pix = (uint32_t)j * (uint32_t)C.width + (uint32_t)i;
+                if (PRIM) prec = primary_table_opaque()[pix];  // in flight during the path start
+                path_begin<Real, false>(C, P, pixel_center<Real>(C, i, j), pix, (uint32_t)(sb.s_base + s));
+                // Wait for the record here, inside the block that issued its load (slot_pixel's
+                // note): pending on the paths around this block, its registers would make later
+                // writes of them wait with vmcnt(0), for the sample records stored before them too.
+                // This is the trip loop's one vector-memory load; on gfx9 the wait also covers the
+                // previous trip's record stores, which the path start has given time to drain.
+                if (PRIM) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (gfx9 encoding)
+            }
+            psec<PP>(pf, PR_NEWPATH);  // item hand-out and path starts
+        } else {
+            if (k >= 0) {
+                path = true;
+                P.rng = (uint64_t)__float_as_uint(g0.x) | ((uint64_t)__float_as_uint(g0.y) << 32);
+                P.o = V3{g1.x, g1.y, g1.z};
+                P.d = V3{g2.x, g2.y, g2.z};
+                P.T = V3{g2.w, g3.x, g3.y};
+                P.bounces = phase;
+                P.em_n = 0;
+            }
+            if (fr == FR_D) {
+                // ---- Dc / Dl: diffuse shading of the queued hits (o = the hit point, d = the face
+                // normal); the new ray stays in registers for the back ----
+                if (lane < nd) {
+                    const int hf = hs_hf(g0.w);
+                    const int h = hf & 0x3fff;
+                    const bool planar = (hf >> 14) & 1, front = (hf >> 15) & 1;
+                    const V3 att = ld3(S.mats[meta_mat(g0.z)].color);  // the Lambertian scatter's attenuation
+                    const bool dterm =
+                        dtop ? shade_diffuse<Real, false, false, PP, 2>(S, C, P, h, planar, front, P.o, P.d, att, cnt, pf)
+                             : shade_diffuse<Real, false, false, PP, 1>(S, C, P, h, planar, front, P.o, P.d, att, cnt, pf);
+                    if (dterm) {
+                        // mixture value cut-off: the level's emission (as computed at the hit: T is unchanged)
                         term = true;
-                        c = miss_color<Real, false, PP>(C, P, err, pf);
+                        c = mulv(ld3(S.mats[S.prims[h].mat].emitted), P.T);
+                    }
+                }
+            } else {
+                psec<PP>(pf, PR_NEWPATH);  // a pure ac trip: the slot loads
+            }
+        }
+        // ---- the back: depth cut-off / roulette, closest hit, miss or hit record + scatter ----
+        bool to_d = false, d_light = false;
+        int hf = 0, dmat = 0;
+        unsigned long long err = 0ull;  // this sample's error flags (its miss)
+        if (path && !term) {
+            term = path_pre<Real, false, PP>(C, P, pf, c);
+            if (!term) {
+                const RayK<Real> ray = make_ray<Real>(P.o, P.d);
+                Real t;
+                int h;
+                V3 att;
+                if (PRIM && fr == FR_N) {  // every lane traces a primary ray
+                    psec<PP>(pf, PR_TILE);  // (no pre-filter section)
+                    h = closest_hit_primary<Real, false>(S, ray, t, prec, cnt);
+                } else if (PP && TRAV == TRAV_BRUTE && C.n_prims <= kBruteMaxPrims)  // section timer
+                    h = closest_hit_brute_nf<Real, false>(S, C.n_prims, ray, t, lot_column(stk), cnt,
+                                                          [&]() { psec<PP>(pf, PR_TILE); });
+                else
+                    h = closest_hit_any<Real, false, TRAV>(S, C.n_prims, ray, t, stk, cnt);
+                psec<PP>(pf, PR_HIT);
+                if (h < 0) {
+                    term = true;
+                    c = miss_color<Real, false, PP>(C, P, err, pf);
+                } else {
+                    V3 p, nrm, emitted, sdir;
+                    bool front, planar;
+                    const int kind = shade_hit<Real, false, false, PP>(S, P, h, t, cnt, pf, p, nrm, front, planar,
+                                                                          emitted, att, sdir, &dmat);
+                    if (kind == SC_NONE) {
+                        term = true;
+                        c = emitted;
                     } else {
-                        V3 p, nrm, emitted, sdir;
-                        bool front, planar;
-                        const int kind = shade_hit<Real, false, false, PP>(S, P, h, t, cnt, pf, p, nrm, front,
-                                                                              planar, emitted, att, sdir, &dmat);
-                        if (kind == SC_NONE) {
-                            term = true;
-                            c = emitted;
+                        ++P.bounces;
+                        P.o = p;
+                        if (kind == SC_SPEC) {
+                            P.T = mulv(P.T, att);
+                            P.d = sdir;
                         } else {
-                            ++P.bounces;
-                            P.o = p;
-                            if (kind == SC_SPEC) {
-                                P.T = mulv(P.T, att);
-                                P.d = sdir;
-                            } else {
-                                to_d = true;
-                                P.d = nrm;  // queued for D: g2 carries the face normal
-                                hf = h | (planar ? (1 << 14) : 0) | (front ? (1 << 15) : 0);
-                                {  // shade_diffuse's first draw and branch, ahead
-                                    uint64_t r = P.rng;
-                                    const Real u0 = uniform<Real>(r);
-                                    const Real rnd = S.mix_total == 1.0 ? u0 : u0 * (Real)S.mix_total;
-                                    d_light = !(rnd < (Real)0.5 || C.n_lights == 0);
-                                }
+                            to_d = true;
+                            P.d = nrm;  // queued for D: g2 carries the face normal
+                            hf = h | (planar ? (1 << 14) : 0) | (front ? (1 << 15) : 0);
+                            {  // shade_diffuse's first draw and branch, ahead
+                                uint64_t r = P.rng;
+                                const Real u0 = uniform<Real>(r);
+                                const Real rnd = S.mix_total == 1.0 ? u0 : u0 * (Real)S.mix_total;
+                                d_light = !(rnd < (Real)0.5 || C.n_lights == 0);
                             }
                         }
                     }
                 }
-                phase = term ? record(c, P.bounces, slot, s, item_end(s, clog2), err) : P.bounces;
-                g0 = make_float4(__uint_as_float((uint32_t)P.rng), __uint_as_float((uint32_t)(P.rng >> 32)),
-                                 pool_meta(phase, clog2, to_d ? dmat : 0), pool_hs(to_d ? hf : 0, s));
-                g1 = make_float4(P.o.x, P.o.y, P.o.z, __int_as_float(slot));
-                g2 = make_float4(P.d.x, P.d.y, P.d.z, P.T.x);
-                g3 = make_float2(P.T.y, P.T.z);
-            } else if (keep) {  // a slot still waiting for a work item
-                g0 = make_float4(0.f, 0.f, pool_meta(PH_ITEM, 0, 0), 0.f);
             }
-            if (keep) {
-                G[k] = g0;
-                G[kPoolK + k] = g1;
-                G[2 * kPoolK + k] = g2;
-                G3[k] = g3;
-            }
-            stack_push(qa, false, an_cnt, keep && !to_d && phase < 0, k);
-            stack_push(qa, true, ac_cnt, keep && !to_d && phase >= 0, k);
-            a_cnt = an_cnt + ac_cnt;
-            stack_push(qd, false, d_cnt, to_d && !d_light, k);
-            stack_push(qd, true, dl_cnt, to_d && d_light, k);
         }
+        // ---- the trip's end: the record, the slot and its queue ----
+        if (path) {
+            phase = term ? record(c, P.bounces, slot, s, item_end(s, clog2), err) : P.bounces;
+            g0 = make_float4(__uint_as_float((uint32_t)P.rng), __uint_as_float((uint32_t)(P.rng >> 32)),
+                             pool_meta(phase, clog2, to_d ? dmat : 0), pool_hs(to_d ? hf : 0, s));
+            g1 = make_float4(P.o.x, P.o.y, P.o.z, __int_as_float(slot));
+            g2 = make_float4(P.d.x, P.d.y, P.d.z, P.T.x);
+            g3 = make_float2(P.T.y, P.T.z);
+        } else if (keep) {  // a slot still waiting for a work item
+            g0 = make_float4(0.f, 0.f, pool_meta(PH_ITEM, 0, 0), 0.f);
+        }
+        if (keep) {
+            G[k] = g0;
+            G[kPoolK + k] = g1;
+            G[2 * kPoolK + k] = g2;
+            G3[k] = g3;
+        }
+        stack_push(qa, false, an_cnt, keep && !to_d && phase < 0, k);
+        stack_push(qa, true, ac_cnt, keep && !to_d && phase >= 0, k);
+        stack_push(qd, false, d_cnt, to_d && !d_light, k);
+        stack_push(qd, true, dl_cnt, to_d && d_light, k);
     }
     PixStats st;
     lb.to(st);
