@@ -642,6 +642,87 @@ int rt_camera_progressive_reproject(rt_camera* cam, rt_camera* prev_cam, const r
  * the whole span guide passes .. unpacked outputs (host copies excluded). Waits for the events. */
 int rt_camera_reproject_times(rt_camera* cam, float* guide_ms, float* reproject_ms, float* total_ms);
 
+/* ---- Accumulation across views: per-pixel history length and variance -------------------------
+ * A view history follows a camera along a path. Per pixel it keeps the accumulated radiance c',
+ * the effective number of samples behind it (the history length L') and the variance V' of the
+ * accumulated mean's illuminance - the meaning of rt_camera_progressive_variance, so the
+ * variance-guided filter consumes it unchanged. One call takes a new view's fresh frame c, its
+ * per-pixel sample counts m (as a float) and variance v, and a history (view, region, guides, c',
+ * L', V'); v and V' are sanitised as the variance filter does (not (>= 0 and finite) -> 0).
+ *   1. Projection, validity and the four taps exactly as the reprojection block above, with one
+ *      more tap condition: L' is finite and > 0 (a pixel that never held a sample is not history).
+ *   2. ws = sum b, acc = sum b c', av = sum b V', al = sum b L' over the taps that count (multiply,
+ *      then add); weight = ws if ws >= min_weight else 0; where weight > 0: h = acc / ws,
+ *      Vh = av / ws, Lh = al / ws, N = min(Lh, max_history).
+ *   3. weight > 0, c finite, m > 0:  den = N + m; out = (h N + c m) / den; g = N / den; a = m / den;
+ *                                    Vout = (g g) Vh + (a a) v; Lout = den
+ *      weight > 0 otherwise:         out = h, Vout = Vh, Lout = N
+ *      weight == 0:                  out = c, Vout = v, Lout = m if c is finite else 0
+ *   4. filter_levels > 0: the returned radiance, rgb and variance_out are the variance-guided
+ *      filter (rt_denoise_variance: levels = filter_levels, sigma_variance, sigma_plane) of out and
+ *      Vout over the region with the new view's guides. length_out / weight_out are never
+ *      filtered, and the history keeps the unfiltered out, Vout and Lout.
+ *   5. Commit: out, Vout, Lout and the new view, guides and region become the history.
+ * An empty history has weight 0 everywhere: the first call commits the fresh frame itself. Built
+ * from fp32 add, subtract, multiply, IEEE divide, floor and min in a fixed order, no fused
+ * multiply-add: the result equals the NumPy restatement tests/temporal_ref.py (the normative
+ * definition) in every bit.
+ *
+ * THE CALLER MUST VARY THE SEED PER VIEW. The path RNG is keyed by (pixel, sample, seed): views
+ * that share a seed have correlated noise, and a static camera with the same seed re-renders the
+ * very same samples - nothing is gained and the carried variance is wrong.
+ *
+ * Limits as the reprojection block (lambert and light surfaces only, unchanged lighting).
+ * max_history (default 256) bounds the weight of the past; it is a design choice, not tuned.
+ *
+ * RT_ERR_INVALID, decided before any device call: negative or non-finite options or
+ * filter_levels outside 0..8; no open session, mode bounces / samples, samples_done < 2; a
+ * missing pointer of the explicit entry; a region that is empty after clamping; "temporal: the
+ * history holds a different scene" (the flattened nodes, primitives, materials, lights and object
+ * map are hashed at the first commit); a history committed on another device. A history of
+ * another image size is allowed. */
+typedef struct rt_history rt_history;
+typedef struct { float normal_min, sigma_plane, min_weight, max_history; int32_t filter_levels; float sigma_variance; } rt_temporal_options;   /* NULL or a zero field = default (0.9, 0.01, 0.25, 256, no filter, 2.0) */
+typedef struct { int32_t width, height; rt_region region; int32_t views, device; uint64_t scene_hash, bytes; rt_view view; } rt_history_info;
+/* Host only: an empty history (views = 0, device -1). The history owns its device buffers - two
+ * sets of colour + length, variance and guides, and the reusable table - on the device of its
+ * first commit; the cameras and sessions it was fed from may be destroyed, and
+ * rt_camera_release_device does not free it. rt_history_destroy does. */
+int rt_history_create(rt_history** out);
+void rt_history_destroy(rt_history* h);
+/* Image size, region and view of the last committed view, the number of committed views, the
+ * device, the scene's hash and the device bytes held. Host only. */
+int rt_history_get_info(const rt_history* h, rt_history_info* info);
+/* The history's radiance (width*height*3 floats), variance and length (width*height floats) to
+ * HOST buffers in the history's own full-frame layout; only its region is written; any may be
+ * NULL. RT_ERR_INVALID while the history is empty. */
+int rt_history_read(rt_history* h, float* radiance, float* variance, float* length);
+/* The open progressive session's device frame, px_samples, state variance and kept guides
+ * accumulated onto the history over the session's region: only the caller's outputs (HOST,
+ * full-frame layout of the camera's image, only the region written, any may be NULL) cross the
+ * bus. commit = 0 leaves the history as it was; the session (state, frame, stats, the bytes of
+ * rt_camera_progressive_save) is never touched. */
+int rt_camera_progressive_accumulate(rt_camera* cam, rt_history* h, const rt_temporal_options* options, int32_t commit,
+                                     uint8_t* rgb, float* radiance, float* variance_out, float* length_out,
+                                     float* weight_out);
+/* Explicit HOST buffers, no camera and no history object (the calling thread's current device),
+ * as rt_reproject: the new view's guides, fresh radiance, px_samples (or the scalar `samples` when
+ * NULL) and variance; the previous view, its region, guides, radiance, variance and length. Every
+ * input pointer but region, prev_region, px_samples and options is required. */
+int rt_temporal_accumulate(int32_t width, int32_t height, const rt_region* region, const float* normal,
+                           const float* position, const float* distance, const int32_t* object, const float* radiance,
+                           const int32_t* px_samples, int32_t samples, const float* variance, const rt_view* prev_view,
+                           const rt_region* prev_region, const float* prev_normal, const float* prev_position,
+                           const float* prev_distance, const int32_t* prev_object, const float* prev_radiance,
+                           const float* prev_variance, const float* prev_length, const uint8_t* reusable,
+                           int32_t n_objects, const rt_temporal_options* options, float* radiance_out,
+                           float* variance_out, float* length_out, float* weight_out, uint8_t* rgb_out);
+/* Device time of the history's last rt_camera_progressive_accumulate from HIP events: the guide
+ * and variance passes (a session computes its guides once), the gather kernel, the filter (0
+ * without one), and the whole span up to the unpacked outputs and the commit's guide copy (host
+ * copies excluded). Waits for the events. */
+int rt_history_times(rt_history* h, float* guide_ms, float* gather_ms, float* filter_ms, float* total_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -585,3 +585,22 @@ void DevCtx::stats_from_words(const unsigned long long* w, rt_render_stats* st) 
 }
 
 }  // namespace rt
+
+void rt_history::release() {
+    if (alloc_device >= 0) {
+        rt::DeviceScope scope;
+        (void)hipSetDevice(alloc_device);
+        for (hipEvent_t& e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        side[0] = Side{};
+        side[1] = Side{};
+        d_reusable.reset();
+    }
+    views = 0, device = -1, alloc_device = -1, front = 0, n_objects = 0;
+    width = height = 0;
+    region = rt_region{};
+    scene_hash = 0;
+    timed = filtered = false;
+}

@@ -23,6 +23,7 @@
 #include "reproject.hpp"
 #include "scene.hpp"
 #include "scene_blob.hpp"
+#include "temporal.hpp"
 
 namespace rt {
 
@@ -310,6 +311,39 @@ struct rt_camera : rt::CamHost {
         prog->prog_free();
         prog = nullptr;
     }
+};
+
+// A view history (rt_history_*, temporal.hpp): device buffers of its own on the device of its first
+// commit, so the cameras and sessions it was fed from may go. Two sets of planes: the kernel reads
+// set `front` and writes the other, and a commit swaps them.
+struct rt_history {
+    std::mutex mu;
+    struct Side {
+        rt::DevBuf<float4> col, gn, gp;  // {r, g, b, length}; the guides of the view it holds
+        rt::DevBuf<float> var;
+        void ensure(size_t n) {
+            for (rt::DevBuf<float4>* p : {&col, &gn, &gp}) p->ensure(n, "hipMalloc(history)");
+            var.ensure(n, "hipMalloc(history)");
+        }
+        size_t bytes() const { return (col.cap + gn.cap + gp.cap) * sizeof(float4) + var.cap * sizeof(float); }
+    } side[2];
+    int front = 0;
+    rt::DevBuf<uint8_t> d_reusable;
+    int32_t n_objects = 0;
+    int32_t views = 0, device = -1;
+    int32_t width = 0, height = 0;
+    rt_region region{};
+    rt_view view{};
+    rt::RpView rp_view{};
+    uint64_t scene_hash = 0;
+    // HIP events of the last session call: start, after the guide and variance passes, after the
+    // gather, after the filter, after the unpack passes and the commit's guide copy
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int alloc_device = -1;  // where the buffers and events live: `device` once a view is committed
+    bool timed = false, filtered = false;
+    // Frees everything on the devices that hold it; the history is empty afterwards.
+    void release();
+    ~rt_history() { release(); }
 };
 
 namespace rt {

@@ -244,6 +244,23 @@ static int two_camera_call(rt_camera* cam, rt_camera* prev_cam, F&& f) {
     }
 }
 
+// Runs f under the history's lock with the single-device entries' error mapping.
+template <class F>
+static int history_call(rt_history* h, F&& f) {
+    if (!h) return set_error(RT_ERR_INVALID, "null history");
+    std::lock_guard<std::mutex> lock(h->mu);
+    try {
+        f();
+        return RT_OK;
+    } catch (const HipError& e) {
+        return set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        return set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_RENDER, e.what());
+    }
+}
+
 template <class T>
 static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
     return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
@@ -1535,6 +1552,317 @@ int rt_camera_reproject_times(rt_camera* cam, float* guide_ms, float* reproject_
         hip_check(hipEventSynchronize(ev[4]), "hipEventSynchronize");
         hip_check(hipEventElapsedTime(guide_ms, ev[0], ev[1]), "hipEventElapsedTime");
         hip_check(hipEventElapsedTime(reproject_ms, ev[2], ev[3]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(total_ms, ev[0], ev[4]), "hipEventElapsedTime");
+    });
+}
+
+// ---- Accumulation across views (temporal.hpp) ---------------------------------------------------
+// rt_temporal_options resolved: a zero field = the default; levels 0 = no filter.
+struct TpOpts {
+    float normal_min, sigma_plane, min_weight, max_history;
+    int32_t levels;
+    float sigma_variance;
+};
+static TpOpts tp_resolve(const rt_temporal_options* o, const std::string& who) {
+    TpOpts r = o ? TpOpts{o->normal_min, o->sigma_plane, o->min_weight, o->max_history, o->filter_levels, o->sigma_variance}
+                 : TpOpts{0.0f, 0.0f, 0.0f, 0.0f, 0, 0.0f};
+    const std::pair<const char*, float> fields[] = {{"normal_min", r.normal_min},
+                                                    {"sigma_plane", r.sigma_plane},
+                                                    {"min_weight", r.min_weight},
+                                                    {"max_history", r.max_history},
+                                                    {"sigma_variance", r.sigma_variance}};
+    for (const auto& f : fields)
+        if (!(f.second >= 0.0f) || !std::isfinite(f.second))
+            throw std::invalid_argument(who + ": " + f.first + " must be positive and finite (0: the default)");
+    if (r.levels < 0 || r.levels > kDenoiseMaxLevels)
+        throw std::invalid_argument(who + ": filter_levels must be 0.." + std::to_string(kDenoiseMaxLevels) +
+                                    " (0: no filter)");
+    if (r.normal_min == 0.0f) r.normal_min = 0.9f;
+    if (r.sigma_plane == 0.0f) r.sigma_plane = 0.01f;
+    if (r.min_weight == 0.0f) r.min_weight = 0.25f;
+    if (r.max_history == 0.0f) r.max_history = 256.0f;
+    if (r.sigma_variance == 0.0f) r.sigma_variance = 2.0f;
+    return r;
+}
+
+// The hash a history keeps of its scene: the arrays rp_same_scene compares.
+static uint64_t tp_scene_hash(const SceneBuild& b) {
+    uint64_t f = fnv1a(b.nodes.data(), b.nodes.size() * sizeof(RtNode));
+    f = fnv1a(b.prims.data(), b.prims.size() * sizeof(RtPrim), f);
+    f = fnv1a(b.mats.data(), b.mats.size() * sizeof(RtMat), f);
+    f = fnv1a(b.lights.data(), b.lights.size() * sizeof(RtLight), f);
+    return fnv1a(b.prim_object.data(), b.prim_object.size() * sizeof(int32_t), f);
+}
+
+// The new view's side of a call: its guides, the fresh frame and sample counts in one layout (row
+// pitch `pitch` pixels, the region at (fx0, fy0)) and the region-packed fresh variance.
+struct TpNew {
+    const float4 *gn, *gp;
+    const float* fresh;
+    const int32_t* pxs;
+    int pitch, fx0, fy0;
+    const float* var;
+    float m;
+};
+
+// The device side of a call: the gather and blend into `out` (weight -> b.dist()), then the
+// caller's outputs - the optional variance-guided filter of out / Vout, else out itself - into
+// b.rad() / b.u8 / b.var, and the length into b.nrm(). pr.width == 0: an empty history. ev (or
+// null): events 2 and 3, recorded after the gather and after the filter. Queued.
+static void tp_run(DnBufs& b, const TpNew& nw, const rt_region& r, const TpHistory& hist, const RpView& view,
+                   const rt_region& pr, const uint8_t* d_reusable, int n_objects, const TpOpts& o, float4* out_col,
+                   float* out_var, bool want_rad, bool want_u8, bool want_var, bool want_len, hipStream_t stream,
+                   hipEvent_t* ev) {
+    const int n = r.width * r.height;
+    TpArgs a{};
+    a.view = view;
+    a.w = r.width, a.h = r.height;
+    a.px0 = pr.x, a.py0 = pr.y, a.pw = pr.width, a.ph = pr.height;
+    a.n_objects = n_objects;
+    a.normal_min = o.normal_min, a.sigma_plane = o.sigma_plane, a.min_weight = o.min_weight, a.max_history = o.max_history;
+    a.pitch = nw.pitch, a.fx0 = nw.fx0, a.fy0 = nw.fy0;
+    a.vpitch = r.width, a.vx0 = 0, a.vy0 = 0;
+    a.m = nw.m;
+    hip_check(launch_temporal(a, nw.gn, nw.gp, hist, d_reusable, nw.fresh, nw.pxs, nw.var, TpOut{out_col, out_var, b.dist()},
+                              stream),
+              "temporal_kernel");
+    if (ev) hip_check(hipEventRecord(ev[2], stream), "hipEventRecord");
+    const bool filter = o.levels > 0 && (want_rad || want_u8 || want_var);
+    if (filter || want_var) {
+        // (the kernel has read the fresh variance, which may be b.var itself)
+        b.var.ensure((size_t)n, "hipMalloc(denoise variance)");
+        hip_check(hipMemcpyAsync(b.var, out_var, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync");
+    }
+    if (filter) {
+        hip_check(launch_denoise_unpack(out_col, n, b.rad(), nullptr, nullptr, stream), "denoise_unpack_kernel");
+        dn_filter(b, nw.gn, nw.gp, b.rad(), r.width, 0, 0, r.width, r.height,
+                  DnOpts{true, o.levels, o.sigma_variance, o.sigma_plane}, want_rad, want_u8, want_var, stream, nullptr);
+    }
+    if (ev) hip_check(hipEventRecord(ev[3], stream), "hipEventRecord");
+    if (!filter && (want_rad || want_u8))
+        hip_check(launch_denoise_unpack(out_col, n, want_rad ? b.rad() : nullptr, want_u8 ? b.u8.p : nullptr, nullptr, stream),
+                  "denoise_unpack_kernel");
+    if (want_len) hip_check(launch_denoise_unpack(out_col, n, nullptr, nullptr, b.nrm(), stream), "denoise_unpack_kernel");
+}
+
+int rt_history_create(rt_history** out) {
+    if (!out) return set_error(RT_ERR_INVALID, "null argument");
+    try {
+        *out = new rt_history();
+        return RT_OK;
+    } catch (const std::exception& e) {
+        return set_error(RT_ERR_RENDER, e.what());
+    }
+}
+
+void rt_history_destroy(rt_history* h) { delete h; }
+
+int rt_history_get_info(const rt_history* h, rt_history_info* info) {
+    if (!h || !info) return set_error(RT_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(const_cast<rt_history*>(h)->mu);
+    *info = rt_history_info{};
+    info->width = h->width;
+    info->height = h->height;
+    info->region = h->region;
+    info->views = h->views;
+    info->device = h->device;
+    info->scene_hash = h->scene_hash;
+    info->bytes = h->side[0].bytes() + h->side[1].bytes() + h->d_reusable.cap;
+    info->view = h->view;
+    return RT_OK;
+}
+
+int rt_history_read(rt_history* h, float* radiance, float* variance, float* length) {
+    return history_call(h, [&] {
+        if (h->views <= 0) throw std::invalid_argument("rt_history_read: the history is empty");
+        DeviceScope scope;
+        hip_check(hipSetDevice(h->device), "hipSetDevice");
+        const hipStream_t stream = nullptr;
+        const rt_history::Side& s = h->side[h->front];
+        const rt_region& r = h->region;
+        const int n = r.width * r.height;
+        DnBufs b;  // staging of this call alone
+        b.ensure((size_t)n);
+        hip_check(launch_denoise_unpack(s.col, n, radiance ? b.rad() : nullptr, nullptr, length ? b.dist() : nullptr, stream),
+                  "denoise_unpack_kernel");
+        dn_download(radiance, b.rad(), 3 * sizeof(float), h->width, r, stream);
+        dn_download(length, b.dist(), sizeof(float), h->width, r, stream);
+        dn_download(variance, s.var, sizeof(float), h->width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_progressive_accumulate(rt_camera* cam, rt_history* h, const rt_temporal_options* options, int32_t commit,
+                                     uint8_t* rgb, float* radiance, float* variance_out, float* length_out,
+                                     float* weight_out) {
+    if (!h) return set_error(RT_ERR_INVALID, "null history");
+    std::lock_guard<std::mutex> hlock(h->mu);
+    return camera_call(cam, [&] {
+        const std::string who = "rt_camera_progressive_accumulate";
+        const TpOpts o = tp_resolve(options, who);
+        DevCtx& c = session_with(cam, who, 2);
+        const uint64_t hash = tp_scene_hash(cam->build);
+        if (h->views > 0 && hash != h->scene_hash) throw std::invalid_argument("temporal: the history holds a different scene");
+        if (h->views > 0 && h->device != c.device)
+            throw std::invalid_argument(who + ": the history was committed on another device");
+        const RtCamera& C = cam->build.cam;
+        DevCtx::ProgSession& P = c.prog;
+        const rt_region r = P.region;
+        const size_t n = (size_t)r.width * r.height;
+        const hipStream_t stream = nullptr;
+        if (h->views == 0 && h->alloc_device != c.device) {
+            h->release();  // (buffers of an uncommitted call elsewhere)
+            h->alloc_device = c.device;
+        }
+        for (hipEvent_t& e : h->ev)
+            if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+        rt_history::Side& back = h->side[h->front ^ 1];
+        const rt_history::Side& front = h->side[h->front];
+        back.ensure(n);
+        if (!h->d_reusable || h->views == 0) {  // (an uncommitted call may have been another scene's)
+            std::vector<uint8_t> t = cam->reusable_objects();
+            h->n_objects = (int32_t)t.size();
+            t.resize(std::max<size_t>(t.size(), 1), 0);
+            h->d_reusable.ensure(t.size(), "hipMalloc(reusable objects)");
+            hip_check(hipMemcpy(h->d_reusable, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        DnBufs& b = c.dn;
+        b.ensure(n);
+        hip_check(hipEventRecord(h->ev[0], stream), "hipEventRecord");
+        session_guides(cam, c, stream);
+        prog_variance_pass(c, stream);
+        hip_check(hipEventRecord(h->ev[1], stream), "hipEventRecord");
+        const bool has = h->views > 0;
+        const TpHistory hist = has ? TpHistory{front.gn, front.gp, front.col, front.var} : TpHistory{};
+        const rt_region pr = has ? h->region : rt_region{0, 0, 0, 0};
+        const TpNew nw{P.d_gn, P.d_gp, P.d_rad, P.d_pxs, C.width, r.x, r.y, b.var, 0.0f};
+        tp_run(b, nw, r, hist, h->rp_view, pr, h->d_reusable, h->n_objects, o, back.col, back.var, radiance != nullptr,
+               rgb != nullptr, variance_out != nullptr, length_out != nullptr, stream, h->ev);
+        if (commit) {
+            // the session may be gone before the next view: the history keeps the guides itself
+            hip_check(hipMemcpyAsync(back.gn, P.d_gn, n * sizeof(float4), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync");
+            hip_check(hipMemcpyAsync(back.gp, P.d_gp, n * sizeof(float4), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync");
+        }
+        hip_check(hipEventRecord(h->ev[4], stream), "hipEventRecord");
+        h->timed = true;
+        h->filtered = o.levels > 0 && (radiance || rgb || variance_out);
+        dn_download(radiance, b.rad(), 3 * sizeof(float), C.width, r, stream);
+        dn_download(rgb, b.u8, 3, C.width, r, stream);
+        dn_download(variance_out, b.var, sizeof(float), C.width, r, stream);
+        dn_download(length_out, b.nrm(), sizeof(float), C.width, r, stream);
+        dn_download(weight_out, b.dist(), sizeof(float), C.width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        if (commit) {
+            h->front ^= 1;
+            h->views += 1;
+            h->device = c.device;
+            h->width = C.width, h->height = C.height;
+            h->region = r;
+            h->scene_hash = hash;
+            (void)rt_camera_get_view(cam, &h->view);
+            h->rp_view = rp_camera_view(cam);
+        }
+    });
+}
+
+int rt_temporal_accumulate(int32_t width, int32_t height, const rt_region* region, const float* normal,
+                           const float* position, const float* distance, const int32_t* object, const float* radiance,
+                           const int32_t* px_samples, int32_t samples, const float* variance, const rt_view* prev_view,
+                           const rt_region* prev_region, const float* prev_normal, const float* prev_position,
+                           const float* prev_distance, const int32_t* prev_object, const float* prev_radiance,
+                           const float* prev_variance, const float* prev_length, const uint8_t* reusable,
+                           int32_t n_objects, const rt_temporal_options* options, float* radiance_out,
+                           float* variance_out, float* length_out, float* weight_out, uint8_t* rgb_out) {
+    const std::string who = "rt_temporal_accumulate";
+    DnBufs nb, pb;
+    rt_history::Side out;
+    DevBuf<float> d_var;
+    DevBuf<uint8_t> d_reusable;
+    int rc = RT_OK;
+    try {
+        if (width <= 0 || height <= 0) throw std::invalid_argument(who + ": width and height must be positive");
+        if (!normal || !position || !distance || !object || !radiance || !variance)
+            throw std::invalid_argument(who + ": normal, position, distance, object, radiance and variance are required");
+        if (!prev_view || !prev_normal || !prev_position || !prev_distance || !prev_object || !prev_radiance ||
+            !prev_variance || !prev_length)
+            throw std::invalid_argument(who + ": prev_view, prev_normal, prev_position, prev_distance, prev_object, "
+                                              "prev_radiance, prev_variance and prev_length are required");
+        if (prev_view->width <= 0 || prev_view->height <= 0)
+            throw std::invalid_argument(who + ": the previous view's width and height must be positive");
+        if (n_objects < 0 || (n_objects > 0 && !reusable))
+            throw std::invalid_argument(who + ": reusable must hold n_objects >= 0 entries");
+        if (samples < 0) throw std::invalid_argument(who + ": samples must not be negative");
+        const TpOpts o = tp_resolve(options, who);
+        const rt_region r = dn_region(region, width, height, who);
+        const rt_region pr = dn_region(prev_region, prev_view->width, prev_view->height, who);
+        const RpView view = rp_view_constants(prev_view->center, prev_view->pixel00, prev_view->du, prev_view->dv,
+                                              prev_view->width, prev_view->height);
+        const hipStream_t stream = nullptr;
+        const int n = r.width * r.height, np = pr.width * pr.height;
+        nb.ensure((size_t)n);
+        pb.ensure((size_t)np);
+        pb.var.ensure((size_t)np, "hipMalloc(history)");
+        out.ensure((size_t)n);
+        d_var.ensure((size_t)n, "hipMalloc(denoise variance)");
+        d_reusable.ensure((size_t)std::max(n_objects, 1), "hipMalloc(reusable objects)");
+        if (n_objects > 0)
+            hip_check(hipMemcpyAsync(d_reusable, reusable, (size_t)n_objects, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+        dn_upload(nb.nrm(), normal, 3 * sizeof(float), width, r, stream);
+        dn_upload(nb.pos(), position, 3 * sizeof(float), width, r, stream);
+        dn_upload(nb.dist(), distance, sizeof(float), width, r, stream);
+        dn_upload(nb.obj, object, sizeof(int32_t), width, r, stream);
+        hip_check(launch_guides_pack(DenoiseGuides{nb.gn, nb.gp}, n, nb.nrm(), nb.pos(), nb.dist(), nb.obj, stream),
+                  "guides_pack_kernel");
+        dn_upload(pb.nrm(), prev_normal, 3 * sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.pos(), prev_position, 3 * sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.dist(), prev_distance, sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.obj, prev_object, sizeof(int32_t), prev_view->width, pr, stream);
+        hip_check(launch_guides_pack(DenoiseGuides{pb.gn, pb.gp}, np, pb.nrm(), pb.pos(), pb.dist(), pb.obj, stream),
+                  "guides_pack_kernel");
+        // (the guides are packed: the staging arrays now carry the frames, the length and the counts)
+        dn_upload(pb.rad(), prev_radiance, 3 * sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.dist(), prev_length, sizeof(float), prev_view->width, pr, stream);
+        dn_upload(pb.var, prev_variance, sizeof(float), prev_view->width, pr, stream);
+        hip_check(launch_temporal_pack(pb.rad(), pb.dist(), np, pb.c0, stream), "temporal_pack_kernel");
+        dn_upload(nb.pos(), radiance, 3 * sizeof(float), width, r, stream);
+        dn_upload(d_var, variance, sizeof(float), width, r, stream);
+        if (px_samples) dn_upload(nb.obj, px_samples, sizeof(int32_t), width, r, stream);
+        const TpNew nw{nb.gn, nb.gp, nb.pos(), px_samples ? nb.obj.p : nullptr, r.width, 0, 0, d_var, (float)samples};
+        tp_run(nb, nw, r, TpHistory{pb.gn, pb.gp, pb.c0, pb.var}, view, pr, d_reusable, n_objects, o, out.col, out.var,
+               radiance_out != nullptr, rgb_out != nullptr, variance_out != nullptr, length_out != nullptr, stream, nullptr);
+        dn_download(radiance_out, nb.rad(), 3 * sizeof(float), width, r, stream);
+        dn_download(rgb_out, nb.u8, 3, width, r, stream);
+        dn_download(variance_out, nb.var, sizeof(float), width, r, stream);
+        dn_download(length_out, nb.nrm(), sizeof(float), width, r, stream);
+        dn_download(weight_out, nb.dist(), sizeof(float), width, r, stream);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    } catch (const HipError& e) {
+        rc = set_error(RT_ERR_DEVICE, e.what());
+    } catch (const std::invalid_argument& e) {
+        rc = set_error(RT_ERR_INVALID, e.what());
+    } catch (const std::exception& e) {
+        rc = set_error(RT_ERR_RENDER, e.what());
+    }
+    nb.free();
+    pb.free();
+    out = rt_history::Side{};
+    d_var.reset();
+    d_reusable.reset();
+    return rc;
+}
+
+int rt_history_times(rt_history* h, float* guide_ms, float* gather_ms, float* filter_ms, float* total_ms) {
+    if (!guide_ms || !gather_ms || !filter_ms || !total_ms) return set_error(RT_ERR_INVALID, "null argument");
+    return history_call(h, [&] {
+        if (!h->timed) throw std::invalid_argument("rt_history_times: no accumulate call yet");
+        DeviceScope scope;
+        hip_check(hipSetDevice(h->alloc_device), "hipSetDevice");
+        hipEvent_t* ev = h->ev;  // guide + variance [0, 1), gather [1, 2), filter [2, 3), outputs + commit [3, 4)
+        hip_check(hipEventSynchronize(ev[4]), "hipEventSynchronize");
+        hip_check(hipEventElapsedTime(guide_ms, ev[0], ev[1]), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(gather_ms, ev[1], ev[2]), "hipEventElapsedTime");
+        *filter_ms = 0.0f;
+        if (h->filtered) hip_check(hipEventElapsedTime(filter_ms, ev[2], ev[3]), "hipEventElapsedTime");
         hip_check(hipEventElapsedTime(total_ms, ev[0], ev[4]), "hipEventElapsedTime");
     });
 }

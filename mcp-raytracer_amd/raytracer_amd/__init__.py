@@ -16,17 +16,22 @@ Camera.render_guides / Camera.denoise / denoise / ProgressiveRender.denoised; a 
 per-pixel variance map (ProgressiveRender.variance, progressive_blob_variance) guides that filter
 when `variance=` is passed to any of them. A previous view's frame is reprojected into a moved
 camera's view by Camera.reproject / reproject / ProgressiveRender.reprojected (Camera.view,
-Camera.reusable_objects), so the first frames of a new view start from the last view's history.
+Camera.reusable_objects), so the first frames of a new view start from the last view's history. A History follows a camera
+along a path on the device: ProgressiveRender.accumulated blends each view's frame onto it by
+per-pixel history lengths and carries a variance the variance-guided filter consumes
+(temporal_accumulate: the same with explicit buffers). Vary `seed` per view.
 """
 from ._lib import RtError, build_id, device_count, progressive_blob_info, progressive_blob_variance
-from .camera import Camera, ProgressiveRender, RenderStats, denoise, reproject, rng_stream
+from .camera import (Camera, History, ProgressiveRender, RenderStats, denoise, reproject, rng_stream,
+                     temporal_accumulate)
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
                      generate_scene_data, generateScene, generateSceneData)
 
 __all__ = [
     "Camera", "ProgressiveRender", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
-    "progressive_blob_info", "progressive_blob_variance", "denoise", "reproject",
+    "progressive_blob_info", "progressive_blob_variance", "denoise", "reproject", "History",
+    "temporal_accumulate",
     "generate_scene_data", "create_camera_from_scene_data", "generate_scene",
     "generate_image_buffer", "divide_into_regions",
     "generateSceneData", "createCameraFromSceneData", "generateScene", "generateImageBuffer",

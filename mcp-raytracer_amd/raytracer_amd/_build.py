@@ -54,6 +54,9 @@ _UNITS = [
     # the reprojection gather: as the filter, every fp32 operation rounds once - the output equals
     # tests/reproject_ref.py in every bit
     ("reproject.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the accumulation across views: the same rule - the output equals tests/temporal_ref.py in
+    # every bit
+    ("temporal.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the primary-ray candidate table's builder: the kernel and the host loop run the same double
     # operations, one rounding each, so the two tables are equal in every bit
     ("primary.hip", ["-ffp-contract=off"], True),
@@ -71,7 +74,7 @@ _UNITS = [
     ("image.cpp", [], False),
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "reproject.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "reproject.hpp", "temporal.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp"]
 _LIBS = ["-lz"]
 

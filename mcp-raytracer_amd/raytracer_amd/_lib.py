@@ -111,6 +111,16 @@ class RtReprojectOptions(C.Structure):
                 ("history_samples", C.c_float)]
 
 
+class RtTemporalOptions(C.Structure):
+    _fields_ = [("normal_min", C.c_float), ("sigma_plane", C.c_float), ("min_weight", C.c_float),
+                ("max_history", C.c_float), ("filter_levels", C.c_int32), ("sigma_variance", C.c_float)]
+
+
+class RtHistoryInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("region", RtRegion), ("views", C.c_int32),
+                ("device", C.c_int32), ("scene_hash", C.c_uint64), ("bytes", C.c_uint64), ("view", RtView)]
+
+
 class RtPrimaryInfo(C.Structure):
     _fields_ = [("available", C.c_int32), ("used", C.c_int32), ("built", C.c_int32), ("min_samples", C.c_int32),
                 ("build_ms", C.c_float)]
@@ -242,6 +252,20 @@ _SIGS = {
                                                   C.c_void_p]),
     "rt_camera_reproject_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_float)]),
+    "rt_history_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "rt_history_destroy": (None, [C.c_void_p]),
+    "rt_history_get_info": (C.c_int, [C.c_void_p, C.POINTER(RtHistoryInfo)]),
+    "rt_history_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_progressive_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtTemporalOptions), C.c_int32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_accumulate": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RtView),
+                                         C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.POINTER(RtTemporalOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "rt_history_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float)]),
 }
 
 _lib = None

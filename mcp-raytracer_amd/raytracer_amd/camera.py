@@ -255,6 +255,142 @@ def reproject(prev_radiance, prev_view, prev_guides, *, normal, position, distan
     return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
 
 
+def _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance):
+    """rt_temporal_options (a zero field = the default; the library validates the rest)."""
+    return _lib.RtTemporalOptions(float(normal_min), float(sigma_plane), float(min_weight), float(max_history),
+                                  int(filter_levels), float(sigma_variance))
+
+
+def temporal_accumulate(prev_radiance, prev_variance, prev_length, prev_view, prev_guides, *, normal, position, distance,
+                        object, reusable, radiance, variance, px_samples=None, samples=None, region=None,
+                        prev_region=None, rgb=None, out=None, variance_out=None, length_out=None, weight_out=None,
+                        filter_levels=0, sigma_variance=2.0, normal_min=0.9, sigma_plane=0.01, min_weight=0.25,
+                        max_history=256.0):
+    """rt_temporal_accumulate: one accumulation step with explicit buffers, no camera and no
+    History. prev_radiance float32 (Hp, Wp, 3), prev_variance / prev_length float32 (Hp, Wp),
+    prev_view as Camera.view() and prev_guides as Camera.render_guides() of the previous view;
+    normal / position / distance / object: the new view's guides; reusable: uint8 per object;
+    radiance float32 (H, W, 3), variance float32 (H, W) and the sample counts (`px_samples` int32
+    (H, W), or one scalar `samples`) of the fresh frame. Returns the accumulated radiance (H, W, 3)
+    - `out`, or a new array that holds the fresh frame outside the region - filtered by the
+    variance-guided filter when filter_levels > 0; `rgb`, `variance_out`, `length_out` and
+    `weight_out` are optional; only the region is written. Equals tests/temporal_ref.py in every
+    bit. Views must be rendered with different seeds."""
+    import numpy as np
+    obj = np.asarray(object)
+    if obj.ndim != 2:
+        raise ValueError("object must have shape (H, W)")
+    H, W = obj.shape
+    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
+    view = _lib.RtView()
+    for k in ("center", "pixel00", "du", "dv"):
+        getattr(view, k)[:] = [float(v) for v in np.asarray(prev_view[k], dtype=np.float32)]
+    view.width, view.height = Wp, Hp
+    g = [_f32_frame(normal, (H, W, 3), "normal"), _f32_frame(position, (H, W, 3), "position"),
+         _f32_frame(distance, (H, W), "distance"), _f32_frame(obj, (H, W), "object")]
+    pg = [_f32_frame(prev_guides["normal"], (Hp, Wp, 3), "normal"),
+          _f32_frame(prev_guides["position"], (Hp, Wp, 3), "position"),
+          _f32_frame(prev_guides["distance"], (Hp, Wp), "distance"),
+          _f32_frame(prev_guides["object"], (Hp, Wp), "object")]
+    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
+    pvar = _f32_frame(prev_variance, (Hp, Wp), "prev_variance")
+    plen = _f32_frame(prev_length, (Hp, Wp), "prev_length")
+    rad = _f32_frame(radiance, (H, W, 3), "radiance")
+    var = _f32_frame(variance, (H, W), "variance")
+    pxs = None if px_samples is None else np.ascontiguousarray(px_samples, dtype=np.int32)
+    if pxs is not None and pxs.size != H * W:
+        raise ValueError(f"px_samples must hold {H}x{W} values, not {pxs.size}")
+    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
+    res = _denoise_out(rad, out)
+    uptr, _keep = _host_ptr(rgb, H * W * 3, "rgb")
+    reg = None if region is None else _region(region)
+    preg = None if prev_region is None else _region(prev_region)
+    opts = _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance)
+    _lib.check(_lib.load().rt_temporal_accumulate(
+        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], rad.ctypes.data,
+        None if pxs is None else pxs.ctypes.data, 0 if samples is None else int(samples), var.ctypes.data, C.byref(view),
+        C.byref(preg) if preg is not None else None, *[a.ctypes.data for a in pg], prad.ctypes.data, pvar.ctypes.data,
+        plen.ctypes.data, reus.ctypes.data if reus.size else None, int(reus.size), C.byref(opts), res.ctypes.data,
+        _out_array(variance_out, np.float32, (H, W), "variance_out"),
+        _out_array(length_out, np.float32, (H, W), "length_out"),
+        _out_array(weight_out, np.float32, (H, W), "weight_out"), uptr))
+    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+
+class History:
+    """A view history (rt_history_*): per pixel the accumulated radiance, the effective number of
+    samples behind it and the variance of the accumulated mean's illuminance, kept on the device
+    and carried from view to view by ProgressiveRender.accumulated. It owns its buffers: the
+    cameras it was fed from may be closed, and Camera.release_device does not free it. Use as a
+    context manager, or close() it."""
+
+    def __init__(self):
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.rt_history_create(C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("the history is closed")
+        return self._h
+
+    @property
+    def info(self) -> dict:
+        """rt_history_get_info: {"width", "height", "region", "views", "device", "scene_hash",
+        "bytes", "view"} of the last committed view (views 0, device -1: empty)."""
+        import numpy as np
+        i = _lib.RtHistoryInfo()
+        _lib.check(self._lib.rt_history_get_info(self._handle(), C.byref(i)))
+        view = {k: np.array(list(getattr(i.view, k)), dtype=np.float32) for k in ("center", "pixel00", "du", "dv")}
+        view.update(width=int(i.view.width), height=int(i.view.height))
+        return {"width": int(i.width), "height": int(i.height),
+                "region": (int(i.region.x), int(i.region.y), int(i.region.width), int(i.region.height)),
+                "views": int(i.views), "device": int(i.device), "scene_hash": int(i.scene_hash), "bytes": int(i.bytes),
+                "view": view}
+
+    @property
+    def views(self) -> int:
+        return self.info["views"]
+
+    def read(self) -> dict:
+        """rt_history_read: {"radiance": float32 (H, W, 3), "variance", "length": float32 (H, W)} in
+        the history's own full-frame layout, zero outside its region."""
+        import numpy as np
+        i = self.info
+        H, W = i["height"], i["width"]
+        out = {"radiance": np.zeros((H, W, 3), np.float32), "variance": np.zeros((H, W), np.float32),
+               "length": np.zeros((H, W), np.float32)}
+        _lib.check(self._lib.rt_history_read(self._handle(), out["radiance"].ctypes.data, out["variance"].ctypes.data,
+                                             out["length"].ctypes.data))
+        return out
+
+    def times(self) -> dict:
+        """Device time of the last ProgressiveRender.accumulated call, from HIP events
+        (rt_history_times): guide + variance passes, the gather kernel, the filter, the whole span."""
+        g, k, f, t = C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        _lib.check(self._lib.rt_history_times(self._handle(), C.byref(g), C.byref(k), C.byref(f), C.byref(t)))
+        return {"guide_ms": float(g.value), "gather_ms": float(k.value), "filter_ms": float(f.value),
+                "total_ms": float(t.value)}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.rt_history_destroy(self._h)
+            self._h = None
+
+    def __enter__(self) -> "History":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Camera:
     """The reference Camera (src/camera.ts:61-472), rendering on MI355X."""
 
@@ -742,6 +878,41 @@ class ProgressiveRender:
         _lib.check(cam._lib.rt_camera_progressive_reproject(cam._h, prev_cam._h,
                                                             C.byref(preg) if preg is not None else None,
                                                             C.byref(opts), prad.ctypes.data, ptr, rptr, wptr))
+        if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
+            return radiance.reshape(shape)
+        return radiance
+
+    def accumulated(self, history: History, rgb=None, radiance=None, *, commit=True, variance_out=None,
+                    length_out=None, weight_out=None, filter_levels=0, sigma_variance=2.0, normal_min=0.9,
+                    sigma_plane=0.01, min_weight=0.25, max_history=256.0):
+        """The session's frame as it stands after the last step, accumulated onto `history`
+        (rt_camera_progressive_accumulate): every pixel's history - gathered from the history's
+        view as reprojected() does - is blended by its own length N = min(length, max_history)
+        against the pixel's own sample count, and a variance is carried along. Nothing is uploaded:
+        the frame, the counts, the state's variance and the guides are the session's device
+        buffers. `commit=True` makes the result the history (its first call commits the frame
+        itself); the session is never touched. `filter_levels > 0` returns the frame through the
+        variance-guided filter driven by the accumulated variance (the history keeps the
+        unfiltered frame). `rgb` (u8 W*H*3), `radiance` (float32 W*H*3), `variance_out`,
+        `length_out`, `weight_out` (float32 (H, W)) are optional caller-owned full-frame buffers;
+        only the region is written. Returns the radiance as a (H, W, 3) array. Needs
+        samples_done >= 2, and every view rendered with its own `seed`: views that share a seed
+        have correlated noise and the carried variance is then wrong."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        import numpy as np
+        cam = self._cam
+        shape = (cam.image_height, cam.image_width, 3)
+        if radiance is None:
+            radiance = np.zeros(shape, np.float32)
+        ptr, _k0 = _host_ptr(rgb, cam.byte_length, "rgb")
+        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
+        opts = _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance)
+        _lib.check(cam._lib.rt_camera_progressive_accumulate(
+            cam._h, history._handle(), C.byref(opts), 1 if commit else 0, ptr, rptr,
+            _out_array(variance_out, np.float32, shape[:2], "variance_out"),
+            _out_array(length_out, np.float32, shape[:2], "length_out"),
+            _out_array(weight_out, np.float32, shape[:2], "weight_out")))
         if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
             return radiance.reshape(shape)
         return radiance
