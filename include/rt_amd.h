@@ -723,6 +723,85 @@ int rt_temporal_accumulate(int32_t width, int32_t height, const rt_region* regio
  * copies excluded). Waits for the events. */
 int rt_history_times(rt_history* h, float* guide_ms, float* gather_ms, float* filter_ms, float* total_ms);
 
+/* ---- Focused steps: the next samples go to the noisiest pixels ---------------------------------
+ * No reference counterpart (the reference gives every pixel the same loop). Opt-in: a session
+ * that never takes a focused step is what it was. tests/focus_ref.py is the normative NumPy
+ * definition of the selection; the device result equals it exactly.
+ *
+ * A focused step of n_samples on the open session:
+ *   1. Score, one fp32 per pixel of the region, from options->source:
+ *        RT_FOCUS_SCORE_VARIANCE  the session's own variance, the value
+ *                                 rt_camera_progressive_variance returns (needs samples_done >= 2);
+ *        RT_FOCUS_SCORE_MAP       `score`: a HOST map, REGION-PACKED (pixel (i, j) of the region
+ *                                 at (j - region.y) * region.width + (i - region.x)) - a
+ *                                 variance_out of the variance-guided filter cut to the region,
+ *                                 or anything else;
+ *        RT_FOCUS_SCORE_HISTORY   `h`'s variance plane; only when the history's last committed
+ *                                 region and image size are the session's and it lives on the
+ *                                 session's device.
+ *      Sanitised as the variance filter does: not (>= 0 and finite) becomes 0.
+ *   2. Eligible: the pixels still sampling (the session's active list) with score > min_score.
+ *      min_score defaults to 0, so a zero score is never chosen.
+ *   3. Budget: K = (active_pixels * permille + 999) / 1000 in integers, permille in 1..1000
+ *      (default 250); capped by max_pixels when that is > 0.
+ *   4. Threshold: T = the K-th largest eligible score, compared as the uint32 bit pattern (which
+ *      orders non-negative finite floats).
+ *   5. Selected: the eligible pixels with score >= T; all of them when at most K are eligible.
+ *      Ties at T are ALL taken, so more than K pixels may be selected, and the selected set is a
+ *      function of the scores alone (the order of the active list is not deterministic).
+ *   6. Nothing eligible: the step renders nothing, changes nothing and returns RT_OK with
+ *      selected = 0.
+ *   7. The selected pixels render the sample indices [samples + focus_done, samples + focus_done
+ *      + n_samples), `samples` being the camera's loop count; focus_done, a cursor of the
+ *      session, then advances by n_samples. samples_done does not move: the plain windows
+ *      [0, samples) are never consumed by a focused step.
+ *   8. The records are settled as a plain step's: in sample order, the convergence check after
+ *      every sample, a pixel finished at `samples` samples and what was rendered past that
+ *      dropped. One resolve pass follows; the outputs are those of rt_camera_progressive_step.
+ *
+ * Consequences.
+ *   - A pixel that was never selected holds samples_done samples and is still bit-identical to
+ *     the one-shot render with `samples: samples_done`: the session's contract holds per pixel.
+ *   - A selected pixel holds more samples than that; px_samples says how many.
+ *     rt_camera_progressive_variance, _denoise_variance and _accumulate use each pixel's own count.
+ *   - active_pixels no longer means "holds samples_done samples" once a focused step has run.
+ *   - Plain and focused steps mix freely. A selected pixel stops at `samples` samples like any
+ *     other and is never visited again.
+ *   - The frame depends on the selected sets only: cutting a focused step in two (the same set
+ *     selected both times) or selecting other pixels beside a pixel does not change it.
+ *   - A session that has taken a focused step that rendered refuses rt_camera_progressive_save
+ *     with RT_ERR_INVALID ("progressive: a focused session cannot be saved"): blob format
+ *     version 1 has no field for focus_done.
+ *
+ * RT_ERR_INVALID, decided before any device call: n_samples outside 1..65535 (the pool kernel
+ * keeps a step's relative sample index in 16 bits); permille outside 1..1000; a negative or
+ * non-finite min_score; a negative max_pixels; an unknown source; RT_FOCUS_SCORE_MAP with a NULL
+ * score, RT_FOCUS_SCORE_HISTORY with a NULL, empty or mismatching history; no open session; mode
+ * bounces / samples; RT_FOCUS_SCORE_VARIANCE while samples_done < 2; samples + focus_done +
+ * n_samples above INT32_MAX. */
+#define RT_FOCUS_SCORE_VARIANCE 0
+#define RT_FOCUS_SCORE_MAP 1
+#define RT_FOCUS_SCORE_HISTORY 2
+typedef struct { int32_t source, permille; float min_score; int32_t max_pixels; } rt_focus_options;   /* NULL = rt_focus_options_default; every field is taken as it is */
+typedef struct {
+    int64_t active;           /* pixels still sampling before the step */
+    int64_t eligible;         /* of them: score > min_score */
+    int64_t selected;         /* of them: score >= threshold (0: the step rendered nothing) */
+    float threshold;          /* T (0 when nothing was eligible) */
+    int32_t focus_done;       /* the session's cursor after the step */
+    int32_t first_sample;     /* the first sample index of the step's window */
+    float select_ms;          /* device time of the selection (score, select, compact) from HIP events */
+} rt_focus_info;
+/* {RT_FOCUS_SCORE_VARIANCE, 250, 0, 0}. Host only. */
+void rt_focus_options_default(rt_focus_options* options);
+/* One focused step (above). rgb / radiance / px_samples / px_bounces / stats as
+ * rt_camera_progressive_step; selected_out: HOST width*height uint8, 1 at every pixel the step
+ * selected and 0 at the other pixels of the region (only the region is written); score and h as
+ * options->source says (the others are ignored); any output and info may be NULL. */
+int rt_camera_progressive_focus(rt_camera* cam, int32_t n_samples, const rt_focus_options* options, const float* score,
+                                rt_history* h, uint8_t* rgb, float* radiance, int32_t* px_samples, int32_t* px_bounces,
+                                uint8_t* selected_out, rt_render_stats* stats, rt_focus_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,8 +224,9 @@ struct DevCtx::LaunchRun {
 
 void DevCtx::launch(const rt_region& region, int tile_group, int tile_groups, int prec, int trav, int count,
                     uint8_t* rgb, float* rad, int32_t* pxs, int32_t* pxb, int packed, hipStream_t stream,
-                    int prog_len) {
+                    const ProgStep* step) {
     const RtCamera& C = build.cam;
+    const int prog_len = step ? step->len : 0;
     const LaunchPlan plan = plan_launch(host, blob, cus, lds_max, clamp_region(region, C.width, C.height), tile_group,
                                         tile_groups, prec, trav, count, prog_len, d_ptab.p != nullptr, pxb != nullptr);
     const LaunchGeom& g = plan.g;
@@ -261,7 +262,7 @@ void DevCtx::launch(const rt_region& region, int tile_group, int tile_groups, in
         return;
     }
     S.lds_pool_off = plan.lds_pool_off;
-    if (prog_len > 0) launch_progressive(r, prog_len);
+    if (prog_len > 0) launch_progressive(r, *step);
     else if (plan.rounds) launch_adaptive_rounds(r);
     else launch_fixed(r);
     n_passes = r.pass;
@@ -406,6 +407,9 @@ void DevCtx::launch_adaptive_rounds(LaunchRun& r) {
 
 void DevCtx::prog_free() {
     if (prog.h_count) (void)hipHostFree(prog.h_count);
+    if (prog.h_fwords) (void)hipHostFree(prog.h_fwords);
+    for (hipEvent_t e : prog.fev)
+        if (e) (void)hipEventDestroy(e);
     prog = ProgSession{};
 }
 
@@ -464,17 +468,32 @@ void DevCtx::prog_start(hipStream_t stream) {
     prog_read(stream);
 }
 
-// One step of the session, from launch(): samples [done, done + len) of the active pixels on
-// the chunked / pool kernel like an adaptive round (16-byte records, error flags in the
-// records), in record passes under the record budget, each settled into the state
-// (pt_settle_kernel); then one resolve pass over the whole region.
-void DevCtx::launch_progressive(LaunchRun& r, int len) {
+void DevCtx::prog_focus_alloc() {
+    ProgSession& P = prog;
+    const size_t px = (size_t)build.cam.width * build.cam.height;
+    P.d_focus.ensure((size_t)P.slots, "hipMalloc(focus list)");
+    P.d_fkey.ensure((size_t)P.slots, "hipMalloc(focus keys)");
+    P.d_fwords.ensure(kFocusWords, "hipMalloc(focus words)");
+    P.d_fmap.ensure((size_t)P.region.width * P.region.height, "hipMalloc(focus score)");
+    P.d_fmask.ensure(px, "hipMalloc(focus mask)");
+    if (!P.h_fwords) hip_check(hipHostMalloc((void**)&P.h_fwords, 4 * sizeof(uint32_t), 0), "hipHostMalloc");
+    for (hipEvent_t& e : P.fev)
+        if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+}
+
+// One step of the session, from launch(): samples [s_base, s_base + len) of the step's pixels (a
+// plain step: the active pixels from samples_done) on the chunked / pool kernel like an
+// adaptive round (16-byte records, error flags in the records), in record passes under the
+// record budget, each settled into the state (pt_settle_kernel); then one resolve pass over the
+// whole region.
+void DevCtx::launch_progressive(LaunchRun& r, const ProgStep& step) {
     ProgSession& P = prog;
     const hipStream_t stream = r.stream;
     SampleBuf& sb = r.sb;
     int& pass = r.pass;
-    const long n_act = P.n_act;
-    sb.s_base = P.done;
+    const long n_act = step.n;
+    const int len = step.len;
+    sb.s_base = step.s_base;
     sb.err_in_rec = 1;
     sb.rec12 = 0;
     sb.stride_slot = 1;
@@ -487,7 +506,7 @@ void DevCtx::launch_progressive(LaunchRun& r, int len) {
     for (long a0 = 0; a0 < n_act; a0 += pass_slots, ++pass) {
         sb.slots = (int32_t)std::min<long>(pass_slots, n_act - a0);
         sb.stride_s = sb.slots;
-        sb.act = P.d_act + a0;
+        sb.act = step.list + a0;
         run_pass(r, pass == 0);
         hip_check(launch_settle(r.S, r.plan.reg, r.out, r.plan.g.tiles_x, sb, pp, stream), "pt_settle_kernel launch");
         if (a0 + pass_slots >= n_act) prog_resolve(stream);  // (timed with the last pass's settle)

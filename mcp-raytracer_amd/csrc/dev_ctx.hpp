@@ -15,6 +15,7 @@
 
 #include "../../include/rt_amd.h"
 #include "denoise.hpp"
+#include "focus.hpp"
 #include "host_util.hpp"
 #include "launch.hpp"
 #include "launch_plan.hpp"
@@ -93,6 +94,15 @@ struct CamHost {
     }
 };
 
+// One step of a progressive session: `len` samples from index s_base of the n slots in `list`.
+// A plain step: the session's active list from samples_done; a focused step: the focus list
+// from samples + focus_done.
+struct ProgStep {
+    const int32_t* list;
+    long n;
+    int32_t s_base, len;
+};
+
 // One device's copy of a camera: the scene blob in that device's HBM, its frame, record and
 // stats buffers, events and (multi-GPU) its stream and tile-packed slabs. A camera keeps one
 // per device it rendered on (rt_camera_render_multi: one per listed device entry), so moving
@@ -168,14 +178,14 @@ struct DevCtx {
     // Launch one render: plan (launch_plan.hpp), then execute; returns after queueing.
     void launch(const rt_region& region, int tile_group, int tile_groups, int prec, int trav, int count,
                 uint8_t* rgb, float* rad, int32_t* pxs, int32_t* pxb, int packed, hipStream_t stream,
-                int prog_len = 0);  // > 0: one step of the progressive session (launch_progressive)
+                const ProgStep* step = nullptr);  // one step of the progressive session (launch_progressive)
 
     // What the passes of one launch share (dev_ctx.cpp).
     struct LaunchRun;
     void run_pass(LaunchRun& r, bool first);
     void launch_fixed(LaunchRun& r);
     void launch_adaptive_rounds(LaunchRun& r);
-    void launch_progressive(LaunchRun& r, int len);
+    void launch_progressive(LaunchRun& r, const ProgStep& step);
 
     // ---- Progressive session (rt_camera_progressive_*) ----------------------------------------
     // State that outlives a call: every region pixel's running PixelStats under its slot (region
@@ -202,6 +212,18 @@ struct DevCtx {
         DevBuf<int32_t> d_pxs, d_pxb;
         DevBuf<float4> d_gn;  // the region's guides (denoise.hpp), computed by the first
         DevBuf<float4> d_gp;  // rt_camera_progressive_denoise of the session
+        // Focused steps (focus.hpp), allocated by the first one: the selected slots, the score
+        // keys of the active entries, the selection's words (counts, T, digit states and
+        // histograms) and their host copy, an uploaded score map, the full-frame selected mask,
+        // and the events around the selection.
+        int32_t focus_done = 0;  // samples the focused steps have used past the camera's `samples`
+        bool focused = false;    // a focused step has rendered: pixels differ in their sample sets
+        DevBuf<int32_t> d_focus;
+        DevBuf<uint32_t> d_fkey, d_fwords;
+        uint32_t* h_fwords = nullptr;
+        DevBuf<float> d_fmap;
+        DevBuf<uint8_t> d_fmask;
+        hipEvent_t fev[2] = {nullptr, nullptr};
     } prog;
 
     // (the caller has made `device` current, or this runs from release(), which has)
@@ -220,6 +242,8 @@ struct DevCtx {
     void prog_read(hipStream_t stream);
     // A new or restored session's first resolve (no path kernel): frame, stats, active list.
     void prog_start(hipStream_t stream);
+    // The focus buffers of the open session (first focused step).
+    void prog_focus_alloc();
 
     // ---- Guides and the a-trous filter (denoise.hpp) -------------------------------------------
     DnBufs dn;                       // one call's buffers (kept between calls)

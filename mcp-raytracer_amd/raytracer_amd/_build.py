@@ -57,6 +57,10 @@ _UNITS = [
     # the accumulation across views: the same rule - the output equals tests/temporal_ref.py in
     # every bit
     ("temporal.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the focused steps' selection: its score is progressive.hpp's prog_variance, evaluated as
+    # progressive.hip evaluates it; the rest is integer work - the selected set equals
+    # tests/focus_ref.py exactly
+    ("focus.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the primary-ray candidate table's builder: the kernel and the host loop run the same double
     # operations, one rounding each, so the two tables are equal in every bit
     ("primary.hip", ["-ffp-contract=off"], True),
@@ -74,7 +78,7 @@ _UNITS = [
     ("image.cpp", [], False),
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "reproject.hpp", "temporal.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "reproject.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp"]
 _LIBS = ["-lz"]
 

@@ -121,6 +121,21 @@ class RtHistoryInfo(C.Structure):
                 ("device", C.c_int32), ("scene_hash", C.c_uint64), ("bytes", C.c_uint64), ("view", RtView)]
 
 
+FOCUS_SCORE_VARIANCE, FOCUS_SCORE_MAP, FOCUS_SCORE_HISTORY = 0, 1, 2
+
+
+class RtFocusOptions(C.Structure):
+    _fields_ = [("source", C.c_int32), ("permille", C.c_int32), ("min_score", C.c_float), ("max_pixels", C.c_int32)]
+
+
+class RtFocusInfo(C.Structure):
+    _fields_ = [("active", C.c_int64), ("eligible", C.c_int64), ("selected", C.c_int64), ("threshold", C.c_float),
+                ("focus_done", C.c_int32), ("first_sample", C.c_int32), ("select_ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RtPrimaryInfo(C.Structure):
     _fields_ = [("available", C.c_int32), ("used", C.c_int32), ("built", C.c_int32), ("min_samples", C.c_int32),
                 ("build_ms", C.c_float)]
@@ -266,6 +281,10 @@ _SIGS = {
                                          C.c_void_p]),
     "rt_history_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float)]),
+    "rt_focus_options_default": (None, [C.POINTER(RtFocusOptions)]),
+    "rt_camera_progressive_focus": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(RtFocusOptions), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(RtRenderStats), C.POINTER(RtFocusInfo)]),
 }
 
 _lib = None

@@ -806,6 +806,62 @@ class ProgressiveRender:
         _lib.check(cam._lib.rt_camera_progressive_step(cam._h, int(n), ptr, rptr, sptr, bptr, C.byref(st)))
         return RenderStats._from_c(st)
 
+    def focus(self, n: int, buffer=None, radiance=None, px_samples=None, px_bounces=None, selected=None, *,
+              score=None, permille=250, min_score=0.0, max_pixels=0) -> RenderStats:
+        """A focused step (rt_camera_progressive_focus): `n` further samples for the noisiest of the
+        pixels still sampling only. `score` ranks them: None - the session's own variance (needs
+        samples_done >= 2); a float32 array, (H, W) or region-shaped - e.g. a `variance_out` of
+        denoised(variance=True); or an rt.History - its variance plane (its last committed region
+        and image size must be the session's). Scores that are not (>= 0 and finite) count as 0;
+        the pixels with score > `min_score` are eligible, and those at or above the K-th largest
+        eligible score are selected, ties included: K = ceil(active_pixels * permille / 1000),
+        capped by `max_pixels` when > 0. They render sample indices from samples + the session's
+        focus cursor on, so samples_done does not move and a pixel never selected stays
+        bit-identical to the one-shot frame with `samples: samples_done`; a selected pixel holds
+        more samples (px_samples says how many) and finishes at the camera's `samples` like any
+        other. Nothing eligible: nothing is rendered or changed. `selected` (u8 W*H) receives 1 at
+        every selected pixel of the region; the other buffers are step()'s. After a focused step
+        that rendered, save() is refused. Returns the RenderStats of the region's frame so far;
+        `focus_info` describes the selection."""
+        if self._cam is None:
+            raise ValueError("the progressive session is closed")
+        import numpy as np
+        cam = self._cam
+        px = cam.image_width * cam.image_height
+        opts = _lib.RtFocusOptions(_lib.FOCUS_SCORE_VARIANCE, int(permille), float(min_score), int(max_pixels))
+        mptr = hptr = None
+        if isinstance(score, History):
+            opts.source = _lib.FOCUS_SCORE_HISTORY
+            hptr = score._handle()
+        elif score is not None:
+            opts.source = _lib.FOCUS_SCORE_MAP
+            _x, _y, rw, rh = self._info().as_dict()["region"]
+            smap = np.asarray(score, dtype=np.float32)
+            if smap.shape == (cam.image_height, cam.image_width):
+                smap = smap[_y:_y + rh, _x:_x + rw]
+            elif smap.shape != (rh, rw):
+                raise ValueError(f"score must be a ({cam.image_height}, {cam.image_width}) or ({rh}, {rw}) array, "
+                                 f"not {smap.shape}")
+            smap = np.ascontiguousarray(smap)
+            mptr = smap.ctypes.data
+        ptr, _k0 = _host_ptr(buffer, cam.byte_length, "buffer")
+        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
+        sptr, _k2 = _host_ptr(px_samples, px * 4, "px_samples")
+        bptr, _k3 = _host_ptr(px_bounces, px * 4, "px_bounces")
+        selptr, _k4 = _host_ptr(selected, px, "selected")
+        st, info = _lib.RtRenderStats(), _lib.RtFocusInfo()
+        _lib.check(cam._lib.rt_camera_progressive_focus(cam._h, int(n), C.byref(opts), mptr, hptr, ptr, rptr, sptr, bptr,
+                                                        selptr, C.byref(st), C.byref(info)))
+        self._focus_info = info.as_dict()
+        return RenderStats._from_c(st)
+
+    @property
+    def focus_info(self) -> Optional[dict]:
+        """The last focus() call's selection (rt_focus_info): active, eligible, selected,
+        threshold, focus_done, first_sample and select_ms (device time of the selection); None
+        before the first call."""
+        return getattr(self, "_focus_info", None)
+
     def variance(self, out=None):
         """The per-pixel variance of the pixel mean's illuminance from the session's running sums
         (rt_camera_progressive_variance): a float32 (H, W) array - `out` when given, else a new
