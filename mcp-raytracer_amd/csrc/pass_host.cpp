@@ -1,0 +1,147 @@
+// The frame passes' shared host side (pass_host.hpp).
+#include "pass_host.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace rt {
+
+float resolve_field(float v, float dflt, const std::string& who, const char* name) {
+    if (!(v >= 0.0f) || !std::isfinite(v))
+        throw std::invalid_argument(who + ": " + name + " must be positive and finite (0: the default)");
+    return v == 0.0f ? dflt : v;
+}
+
+GatherOpts gather_resolve(float normal_min, float sigma_plane, float min_weight, const std::string& who) {
+    GatherOpts o;
+    o.normal_min = resolve_field(normal_min, 0.9f, who, "normal_min");
+    o.sigma_plane = resolve_field(sigma_plane, 0.01f, who, "sigma_plane");
+    o.min_weight = resolve_field(min_weight, 0.25f, who, "min_weight");
+    return o;
+}
+
+constexpr long kDenoiseMaxPixels = 1l << 28;
+rt_region dn_region(const rt_region* region, int32_t width, int32_t height, const std::string& who) {
+    const rt_region r = clamp_region(region ? *region : rt_region{0, 0, width, height}, width, height);
+    if (region_empty(r)) throw std::invalid_argument(who + ": the region is empty after clamping to the image");
+    if ((long)r.width * r.height > kDenoiseMaxPixels) throw std::invalid_argument(who + ": the region has too many pixels");
+    return r;
+}
+
+void RegionIo::up(void* dev, const void* host, size_t elem) const {
+    const size_t off = ((size_t)r.y * width + r.x) * elem;
+    hip_check(hipMemcpy2DAsync(dev, (size_t)r.width * elem, (const char*)host + off, (size_t)width * elem,
+                               (size_t)r.width * elem, r.height, hipMemcpyHostToDevice, stream),
+              "hipMemcpy2DAsync");
+}
+void RegionIo::down(void* host, const void* dev, size_t elem) const {
+    if (!host) return;
+    const size_t off = ((size_t)r.y * width + r.x) * elem;
+    hip_check(hipMemcpy2DAsync((char*)host + off, (size_t)width * elem, dev, (size_t)r.width * elem,
+                               (size_t)r.width * elem, r.height, hipMemcpyDeviceToHost, stream),
+              "hipMemcpy2DAsync");
+}
+
+void upload_guides(DnBufs& b, const RegionIo& io, const float* normal, const float* position, const float* distance,
+                   const int32_t* object) {
+    io.up(b.nrm(), normal, 3 * sizeof(float));
+    io.up(b.pos(), position, 3 * sizeof(float));
+    io.up(b.dist(), distance, sizeof(float));
+    io.up(b.obj, object, sizeof(int32_t));
+    hip_check(launch_guides_pack(DenoiseGuides{b.gn, b.gp}, io.n(), b.nrm(), b.pos(), b.dist(), b.obj, io.stream),
+              "guides_pack_kernel");
+}
+
+void upload_reusable(DevBuf<uint8_t>& d, const uint8_t* reusable, int32_t n_objects, hipStream_t stream) {
+    d.ensure((size_t)std::max(n_objects, 1), "hipMalloc(reusable objects)");
+    if (n_objects > 0)
+        hip_check(hipMemcpyAsync(d, reusable, (size_t)n_objects, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+}
+
+void session_radiance(rt_camera* cam, const std::string& who) {
+    if (cam->build.cam.mode != MODE_DEFAULT)
+        throw std::invalid_argument(who + ": the frames of mode bounces / samples are not radiance");
+}
+
+DevCtx& session_host(rt_camera* cam, const std::string& who, int min_samples) {
+    DevCtx& c = cam->session(who.c_str());
+    session_radiance(cam, who);
+    if (c.prog.done < min_samples)
+        throw std::invalid_argument(who + ": a variance needs at least 2 samples per pixel, the session has " +
+                                    std::to_string(c.prog.done) + " (samples_done < 2)");
+    return c;
+}
+
+void session_on_device(const DevCtx& c, const std::string& who) {
+    int dev = 0;
+    hip_check(hipGetDevice(&dev), "hipGetDevice");
+    if (dev != c.device) throw std::invalid_argument(who + ": the session lives on another device");
+}
+
+DevCtx& session_with(rt_camera* cam, const std::string& who, int min_samples) {
+    DevCtx& c = session_host(cam, who, min_samples);
+    session_on_device(c, who);
+    return c;
+}
+
+void session_guides(rt_camera* cam, DevCtx& c, hipStream_t stream) {
+    DevCtx::ProgSession& P = c.prog;
+    if (P.d_gn) return;
+    const size_t n = (size_t)P.region.width * P.region.height;
+    try {
+        P.d_gn.ensure(n, "hipMalloc(session guides)");
+        P.d_gp.ensure(n, "hipMalloc(session guides)");
+        c.launch_guide_pass(P.region, cam->traversal, DenoiseGuides{P.d_gn, P.d_gp}, stream);
+    } catch (...) {
+        P.d_gn.reset();
+        P.d_gp.reset();
+        throw;
+    }
+}
+
+void prog_variance_pass(DevCtx& c, hipStream_t stream) {
+    DevCtx::ProgSession& P = c.prog;
+    c.dn.var.ensure((size_t)P.region.width * P.region.height, "hipMalloc(denoise variance)");
+    const int tiles_x = std::max((P.region.width + kTile - 1) / kTile, 1);
+    hip_check(launch_prog_variance(P.d_state, (int)P.slots, c.prog_reg(), tiles_x, c.dn.var, stream),
+              "prog_variance_kernel");
+}
+
+void prog_copy_out(const DevCtx& c, void* host, const void* dev, size_t elem, hipStream_t stream) {
+    if (!host) return;
+    const rt_region& r = c.prog.region;
+    const size_t pitch = (size_t)c.build.cam.width * elem;
+    const size_t off = ((size_t)r.y * c.build.cam.width + r.x) * elem;
+    hip_check(hipMemcpy2DAsync((char*)host + off, pitch, (const char*)dev + off, pitch, (size_t)r.width * elem, r.height,
+                               hipMemcpyDeviceToHost, stream),
+              "hipMemcpy2DAsync");
+}
+
+void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0, int w,
+               int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream, hipEvent_t* ev) {
+    int e = 0;
+    auto mark = [&] {
+        if (ev) hip_check(hipEventRecord(ev[e++], stream), "hipEventRecord");
+    };
+    mark();
+    hip_check(launch_denoise_pack(rad, pitch_px, x0, y0, w, h, gn, o.sigma_plane, o.var ? b.var.p : nullptr, b.c0, b.fn,
+                                  stream),
+              "denoise_pack_kernel");
+    mark();
+    // the level's scalar, in double on the host, rounded to fp32 once: sigma_variance^2, or
+    // 4^level / sigma_color^2
+    const double s2 = (double)o.sigma * (double)o.sigma;
+    float4 *src = b.c0, *dst = b.c1;
+    for (int lv = 0; lv < o.levels; ++lv) {
+        const float ks = (float)(o.var ? s2 : std::ldexp(1.0, 2 * lv) / s2);
+        hip_check(launch_denoise_level(o.var, src, dst, b.fn, gp, w, h, 1 << lv, ks, stream), "denoise kernel");
+        mark();
+        std::swap(src, dst);
+    }
+    hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8.p : nullptr,
+                                    o.var && want_var ? b.var.p : nullptr, stream),
+              "denoise_unpack_kernel");
+    mark();
+}
+
+}  // namespace rt

@@ -1,0 +1,113 @@
+// What the frame passes' ABI units (api_denoise / api_reproject / api_temporal / api_focus.cpp)
+// share on the host: option fields, the region check and its copies, the guide and reusable-table
+// uploads, the open session's checks and passes, the filter's launch sequence and the common
+// head of the gather kernels' arguments.
+#pragma once
+
+#include <string>
+
+#include "api_call.hpp"
+
+namespace rt {
+
+// An option field where zero means `dflt`: anything else must not be negative and be finite.
+float resolve_field(float v, float dflt, const std::string& who, const char* name);
+
+// The fields of rt_denoise_options / rt_denoise_var_options as the caller gave them; var: the
+// variance-guided filter, whose sigma is sigma_variance (the plain one's: sigma_color).
+struct DnOpts {
+    bool var;
+    int32_t levels;
+    float sigma, sigma_plane;
+};
+
+// The three thresholds rt_reproject_options and rt_temporal_options share, resolved.
+struct GatherOpts {
+    float normal_min, sigma_plane, min_weight;
+};
+GatherOpts gather_resolve(float normal_min, float sigma_plane, float min_weight, const std::string& who);
+
+// `region` (NULL: the whole image) clamped to a width x height image; empty: an argument error.
+rt_region dn_region(const rt_region* region, int32_t width, int32_t height, const std::string& who);
+
+// Queued copies between a host array in full-frame layout (`elem` bytes per pixel, image width
+// `width`) and a region-packed device array: the rows of region `r` only. down: a null host
+// array is an output the caller did not ask for.
+struct RegionIo {
+    int32_t width;
+    rt_region r;
+    hipStream_t stream;
+    int n() const { return r.width * r.height; }
+    void up(void* dev, const void* host, size_t elem) const;
+    void down(void* host, const void* dev, size_t elem) const;
+};
+
+// The four guide arrays of io's region through b's staging arrays (nrm / pos / dist / obj), then
+// packed into b.gn / b.gp. Queued: the staging arrays may be reused by whatever is queued after.
+void upload_guides(DnBufs& b, const RegionIo& io, const float* normal, const float* position, const float* distance,
+                   const int32_t* object);
+
+// The caller's reusable table (n_objects >= 0 entries) into d, at least one byte. Queued.
+void upload_reusable(DevBuf<uint8_t>& d, const uint8_t* reusable, int32_t n_objects, hipStream_t stream);
+
+// The open session's frames must be radiance.
+void session_radiance(rt_camera* cam, const std::string& who);
+// The open session, whose state holds radiance and at least min_samples samples per pixel (2: a
+// variance); no device call.
+DevCtx& session_host(rt_camera* cam, const std::string& who, int min_samples);
+// The session must live on the current device.
+void session_on_device(const DevCtx& c, const std::string& who);
+// Both: argument errors first, then the device check.
+DevCtx& session_with(rt_camera* cam, const std::string& who, int min_samples);
+// The session's guides: computed once (queued), freed with the session.
+void session_guides(rt_camera* cam, DevCtx& c, hipStream_t stream);
+// The session's state -> c.dn.var (region-packed); queued.
+void prog_variance_pass(DevCtx& c, hipStream_t stream);
+// Queues the copy of the session region's rows of a full-frame device array (`elem` bytes per
+// pixel) into the caller's host array of the same layout.
+void prog_copy_out(const DevCtx& c, void* host, const void* dev, size_t elem, hipStream_t stream);
+
+// The filter over a w x h region whose guides are gn / gp: colour and fn from `rad` (row pitch
+// `pitch_px` pixels, region at (x0, y0)) and, variance-guided, from the region-packed b.var; one
+// launch per level over the ping-pong pair, then the result into b.rad() / b.u8 and, when
+// want_var, the filtered variance into b.var (region-packed). `o` is resolved. ev (or null):
+// levels + 3 events, recorded before the pack pass, after it, after every level and after the
+// unpack pass. Queued.
+void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0, int w,
+               int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream, hipEvent_t* ev);
+
+inline RpView rp_camera_view(const rt_camera* cam) {
+    const RtCamera& C = cam->build.cam;
+    return rp_view_constants(C.center, C.pixel00, C.du, C.dv, C.width, C.height);
+}
+
+// The new view's side of a gather: its guides, and the fresh frame and sample counts to blend
+// (null: history only) in one layout - row pitch `pitch` pixels, the region at (fx0, fy0) - with
+// the scalar sample count m. The accumulation adds the region-packed fresh variance.
+struct RpNew {
+    const float4 *gn, *gp;
+    const float* fresh;
+    const int32_t* pxs;
+    int pitch, fx0, fy0;
+    float m;
+};
+struct TpNew : RpNew {
+    const float* var;
+};
+
+// The head RpArgs and TpArgs have in common; the rest is zero.
+template <class Args>
+Args gather_args(const RpView& view, const rt_region& r, const rt_region& pr, int n_objects, const GatherOpts& o,
+                 const RpNew& nw) {
+    Args a{};
+    a.view = view;
+    a.w = r.width, a.h = r.height;
+    a.px0 = pr.x, a.py0 = pr.y, a.pw = pr.width, a.ph = pr.height;
+    a.n_objects = n_objects;
+    a.normal_min = o.normal_min, a.sigma_plane = o.sigma_plane, a.min_weight = o.min_weight;
+    a.pitch = nw.pitch, a.fx0 = nw.fx0, a.fy0 = nw.fy0;
+    a.m = nw.m;
+    return a;
+}
+
+}  // namespace rt

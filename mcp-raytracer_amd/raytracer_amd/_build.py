@@ -68,6 +68,13 @@ _UNITS = [
     ("png.hip", [], True),
     # the C ABI and the host side of a launch: compiled as HIP for pt_kernel.hpp's types
     ("rt_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    # the frame passes' ABI units, with rt_api.cpp's flags: reproject.hpp's rp_view_constants and
+    # dn_filter's per-level scalar are host computations that must not be contracted
+    ("pass_host.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("api_denoise.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("api_reproject.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("api_temporal.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    ("api_focus.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("dev_ctx.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("launch_plan.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("multi_gpu.cpp", ["-ffp-contract=off", "-x", "hip"], True),
@@ -79,7 +86,7 @@ _UNITS = [
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
             "reproject.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
-            "dev_ctx.hpp"]
+            "dev_ctx.hpp", "api_call.hpp", "pass_host.hpp"]
 _LIBS = ["-lz"]
 
 

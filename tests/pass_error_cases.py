@@ -1,0 +1,274 @@
+"""The argument-error cases of the frame passes' C entries (filter, reprojection, accumulation,
+focused steps), at the raw ABI: one fault per row, plus rows with two faults that pin which error
+wins. tests/golden/make_pass_errors.py records (return code, rt_last_error) of every row;
+tests/test_pass_errors.py replays them. Everything is a 16x16 Cornell camera (samples 4, depth 4)
+and 16x16 zero frames."""
+import ctypes as C
+import json
+from pathlib import Path
+
+import numpy as np
+
+GOLDEN = Path(__file__).resolve().parent / "golden"
+EMPTY_REGIONS = [(16, 0, 4, 4), (0, 0, 0, 5), (-8, -8, 8, 8)]
+BAD = {"-0.5": -0.5, "nan": float("nan"), "inf": float("inf")}
+RO = {"width": 16, "samples": 4, "depth": 4}
+
+# parameter kinds - i: int32; region: rt_region* (None: NULL); Rt*: the options struct (None: NULL,
+# a dict: its fields over zeros - over rt_focus_options_default for the focus options); in: a
+# required input array; opt / out: an optional array (NULL); view: the previous rt_view; reuse: the
+# reusable table; cam / prev_cam / hist: handles.
+_GUIDES = [(n, "in") for n in ("normal", "position", "distance", "object")]
+_PREV_GUIDES = [("prev_" + n, "in") for n in ("normal", "position", "distance", "object")]
+ENTRIES = {
+    "rt_denoise": [("width", "i"), ("height", "i"), ("region", "region"), ("options", "RtDenoiseOptions"),
+                   ("radiance", "in"), *_GUIDES, ("radiance_out", "out"), ("rgb_out", "out")],
+    "rt_denoise_variance": [("width", "i"), ("height", "i"), ("region", "region"), ("options", "RtDenoiseVarOptions"),
+                            ("radiance", "in"), ("variance", "in"), *_GUIDES, ("radiance_out", "out"),
+                            ("variance_out", "out"), ("rgb_out", "out")],
+    "rt_camera_denoise": [("cam", "cam"), ("region", "region"), ("options", "RtDenoiseOptions"), ("radiance", "in"),
+                          ("radiance_out", "out"), ("rgb_out", "out")],
+    "rt_camera_denoise_variance": [("cam", "cam"), ("region", "region"), ("options", "RtDenoiseVarOptions"),
+                                   ("radiance", "in"), ("variance", "in"), ("radiance_out", "out"),
+                                   ("variance_out", "out"), ("rgb_out", "out")],
+    "rt_reproject": [("width", "i"), ("height", "i"), ("region", "region"), *_GUIDES, ("prev_view", "view"),
+                     ("prev_region", "region"), ("prev_radiance", "in"), *_PREV_GUIDES, ("reusable", "reuse"),
+                     ("n_objects", "i"), ("options", "RtReprojectOptions"), ("radiance", "opt"), ("px_samples", "opt"),
+                     ("samples", "i"), ("history_out", "out"), ("weight_out", "out"), ("radiance_out", "out"),
+                     ("rgb_out", "out")],
+    "rt_camera_reproject": [("cam", "cam"), ("region", "region"), ("prev_cam", "prev_cam"), ("prev_region", "region"),
+                            ("options", "RtReprojectOptions"), ("prev_radiance", "in"), ("radiance", "opt"),
+                            ("px_samples", "opt"), ("samples", "i"), ("history_out", "out"), ("weight_out", "out"),
+                            ("radiance_out", "out"), ("rgb_out", "out")],
+    "rt_temporal_accumulate": [("width", "i"), ("height", "i"), ("region", "region"), *_GUIDES, ("radiance", "in"),
+                               ("px_samples", "opt"), ("samples", "i"), ("variance", "in"), ("prev_view", "view"),
+                               ("prev_region", "region"), *_PREV_GUIDES, ("prev_radiance", "in"),
+                               ("prev_variance", "in"), ("prev_length", "in"), ("reusable", "reuse"), ("n_objects", "i"),
+                               ("options", "RtTemporalOptions"), ("radiance_out", "out"), ("variance_out", "out"),
+                               ("length_out", "out"), ("weight_out", "out"), ("rgb_out", "out")],
+    # the session entries (the CPU rows: no session is open)
+    "rt_camera_progressive_denoise": [("cam", "cam"), ("options", "RtDenoiseOptions"), ("rgb", "out"), ("radiance", "out")],
+    "rt_camera_progressive_denoise_variance": [("cam", "cam"), ("options", "RtDenoiseVarOptions"), ("rgb", "out"),
+                                               ("radiance", "out"), ("variance_out", "out")],
+    "rt_camera_progressive_variance": [("cam", "cam"), ("variance", "in")],
+    "rt_camera_progressive_reproject": [("cam", "cam"), ("prev_cam", "prev_cam"), ("prev_region", "region"),
+                                        ("options", "RtReprojectOptions"), ("prev_radiance", "in"), ("rgb", "out"),
+                                        ("radiance", "out"), ("weight_out", "out")],
+    "rt_camera_progressive_accumulate": [("cam", "cam"), ("h", "hist"), ("options", "RtTemporalOptions"), ("commit", "i"),
+                                         ("rgb", "out"), ("radiance", "out"), ("variance_out", "out"),
+                                         ("length_out", "out"), ("weight_out", "out")],
+    "rt_camera_progressive_focus": [("cam", "cam"), ("n_samples", "i"), ("options", "RtFocusOptions"), ("score", "opt"),
+                                    ("h", "opt_hist"), ("rgb", "out"), ("radiance", "out"), ("px_samples", "out"),
+                                    ("px_bounces", "out"), ("selected_out", "out"), ("stats", "out"), ("info", "out")],
+}
+_INT_DEFAULTS = {"width": 16, "height": 16, "n_objects": 1, "samples": 4, "commit": 1, "n_samples": 1}
+_REQUIRED = ("in", "view", "reuse", "cam", "prev_cam", "hist")
+FOCUS = "rt_camera_progressive_focus"
+
+
+def cases():
+    """[(id, entry, overrides)]: overrides by parameter name - None: NULL; a 4-tuple: a region; a
+    dict: option fields (floats as BAD's keys); "w0": a previous view of width 0; "other": a camera
+    of another scene; "hist": a history; an int."""
+    from raytracer_amd import _lib
+    out = []
+
+    def add(entry, label, **ov):
+        out.append((f"{entry}:{label}", entry, ov))
+
+    for entry, params in ENTRIES.items():
+        names = [n for n, _ in params]
+        for n, kind in params:
+            if kind in _REQUIRED:
+                add(entry, f"no {n}", **{n: None})
+        opts = dict(params)["options"] if "options" in names else None
+        if opts and entry != FOCUS:
+            for f, t in getattr(_lib, opts)._fields_:
+                for v in (list(BAD) if t is C.c_float else [-1, 9]):
+                    add(entry, f"{f}={v}", options={f: v})
+        for key in ("region", "prev_region"):
+            if key in names:
+                for r in EMPTY_REGIONS:
+                    add(entry, f"{key}={r}", **{key: r})
+        if "samples" in names:
+            add(entry, "samples=-1", samples=-1)
+        if "n_objects" in names:
+            add(entry, "n_objects=-1", n_objects=-1)
+        if "prev_view" in names:
+            add(entry, "prev_view width 0", prev_view="w0")
+        if "prev_cam" in names:
+            add(entry, "different scenes", prev_cam="other")
+    for v in (0, 65536):
+        add(FOCUS, f"n_samples={v}", n_samples=v)
+    for v in (0, 1001):
+        add(FOCUS, f"permille={v}", options={"permille": v})
+    add(FOCUS, "min_score=-0.5", options={"min_score": "-0.5"})
+    add(FOCUS, "max_pixels=-1", options={"max_pixels": -1})
+    add(FOCUS, "bad source", options={"source": 7})
+    add(FOCUS, "map source without a map", options={"source": 1})
+    add(FOCUS, "history source without a history", options={"source": 2})
+
+    # two faults in one call: which one is named
+    for e, sig in (("rt_denoise", "sigma_color"), ("rt_denoise_variance", "sigma_variance"),
+                   ("rt_camera_denoise", "sigma_color"), ("rt_camera_denoise_variance", "sigma_variance")):
+        add(e, "levels=9 + sigma_plane=-0.5", options={"levels": 9, "sigma_plane": "-0.5"})
+        add(e, f"{sig}=nan + sigma_plane=inf", options={sig: "nan", "sigma_plane": "inf"})
+        add(e, "sigma_plane=-0.5 + empty region", options={"sigma_plane": "-0.5"}, region=EMPTY_REGIONS[0])
+        add(e, "no radiance + levels=9", radiance=None, options={"levels": 9})
+    add("rt_denoise", "no normal + width 0", normal=None, width=0)
+    for e in ("rt_reproject", "rt_camera_reproject"):
+        add(e, "sigma_plane=-0.5 + empty region", options={"sigma_plane": "-0.5"}, region=EMPTY_REGIONS[0])
+        add(e, "no prev_radiance + normal_min=nan", prev_radiance=None, options={"normal_min": "nan"})
+        add(e, "samples=-1 + min_weight=inf", samples=-1, options={"min_weight": "inf"})
+        add(e, "empty region + empty prev_region", region=EMPTY_REGIONS[1], prev_region=EMPTY_REGIONS[2])
+        add(e, "history_samples=-0.5 + normal_min=-0.5", options={"history_samples": "-0.5", "normal_min": "-0.5"})
+    add("rt_reproject", "n_objects=-1 + no prev_radiance", n_objects=-1, prev_radiance=None)
+    add("rt_reproject", "prev_view width 0 + n_objects=-1", prev_view="w0", n_objects=-1)
+    add("rt_reproject", "no object + no prev_view", object=None, prev_view=None)
+    add("rt_camera_reproject", "sigma_plane=inf + different scenes", options={"sigma_plane": "inf"}, prev_cam="other")
+    add("rt_camera_reproject", "empty prev_region + different scenes", prev_region=EMPTY_REGIONS[0], prev_cam="other")
+    add("rt_temporal_accumulate", "filter_levels=9 + sigma_plane=-0.5", options={"filter_levels": 9, "sigma_plane": "-0.5"})
+    add("rt_temporal_accumulate", "filter_levels=-1 + sigma_variance=nan",
+        options={"filter_levels": -1, "sigma_variance": "nan"})
+    add("rt_temporal_accumulate", "max_history=inf + empty region", options={"max_history": "inf"}, region=EMPTY_REGIONS[2])
+    add("rt_temporal_accumulate", "samples=-1 + normal_min=nan", samples=-1, options={"normal_min": "nan"})
+    add("rt_temporal_accumulate", "no prev_length + min_weight=-0.5", prev_length=None, options={"min_weight": "-0.5"})
+    add("rt_temporal_accumulate", "empty prev_region + filter_levels=9", prev_region=EMPTY_REGIONS[0],
+        options={"filter_levels": 9})
+    add("rt_camera_progressive_denoise", "levels=9 + sigma_plane=-0.5", options={"levels": 9, "sigma_plane": "-0.5"})
+    add("rt_camera_progressive_denoise_variance", "levels=9 + sigma_plane=-0.5",
+        options={"levels": 9, "sigma_plane": "-0.5"})
+    add("rt_camera_progressive_variance", "no variance + no cam", variance=None, cam=None)
+    add("rt_camera_progressive_reproject", "sigma_plane=nan + different scenes", options={"sigma_plane": "nan"},
+        prev_cam="other")
+    add("rt_camera_progressive_reproject", "no prev_radiance + empty prev_region", prev_radiance=None,
+        prev_region=EMPTY_REGIONS[0])
+    add("rt_camera_progressive_accumulate", "filter_levels=9 + sigma_plane=-0.5",
+        options={"filter_levels": 9, "sigma_plane": "-0.5"})
+    add("rt_camera_progressive_accumulate", "no h + normal_min=nan", h=None, options={"normal_min": "nan"})
+    add(FOCUS, "n_samples=0 + permille=0", n_samples=0, options={"permille": 0})
+    add(FOCUS, "history source without a history + min_score=-0.5", options={"source": 2, "min_score": "-0.5"})
+    add(FOCUS, "map source without a map + max_pixels=-1", options={"source": 1, "max_pixels": -1})
+    add(FOCUS, "empty history + no session", options={"source": 2}, h="hist")
+    assert len({c[0] for c in out}) == len(out)
+    return out
+
+
+class Env:
+    """The cameras, history and frames the rows are called with."""
+
+    def __init__(self, rt, render_options=RO):
+        from raytracer_amd import _lib
+        self._lib = _lib
+        self.lib = _lib.load()
+        scene = lambda name: json.loads((GOLDEN / f"scene_{name}.json").read_text())["scene"]  # noqa: E731
+        self.cam = rt.create_camera_from_scene_data(scene("cornell"), render_options)
+        self.prev = rt.create_camera_from_scene_data(scene("cornell"), RO)
+        self.other = rt.create_camera_from_scene_data(scene("default"), RO)
+        self.hist = rt.History()
+        self.zeros = np.zeros(16 * 16 * 3, np.float32)
+        self.ones = np.ones(1, np.uint8)
+
+    def call(self, entry, ov):
+        """(return code, rt_last_error) of `entry` with the overrides applied. Beyond cases()'s
+        values an override may be a C-contiguous array (its pointer is passed) or, for the view, a
+        dict as Camera.view() gives it: the GPU suites' raw calls with chosen outputs."""
+        lib, _lib = self.lib, self._lib
+        keep, args = [], []
+        for name, kind in ENTRIES[entry]:
+            has, v = name in ov, ov.get(name)
+            if kind == "i":
+                a = v if has else _INT_DEFAULTS[name]
+            elif kind == "region":
+                a = C.byref(_lib.RtRegion(*v)) if v else None
+            elif kind.startswith("Rt"):
+                a = None
+                if v is not None:
+                    o = getattr(_lib, kind)()
+                    if kind == "RtFocusOptions":
+                        lib.rt_focus_options_default(C.byref(o))
+                    for f, x in v.items():
+                        setattr(o, f, BAD.get(x, x))
+                    keep.append(o)
+                    a = C.byref(o)
+            elif isinstance(v, np.ndarray):  # a caller's array, any array parameter
+                assert v.flags["C_CONTIGUOUS"]
+                a = v.ctypes.data
+            elif kind == "in":
+                a = None if has else self.zeros.ctypes.data
+            elif kind == "view":
+                a = None
+                if not (has and v is None):
+                    view = _lib.RtView()
+                    assert lib.rt_camera_get_view(self.prev._h, C.byref(view)) == 0
+                    if v == "w0":
+                        view.width = 0
+                    elif isinstance(v, dict):  # as Camera.view()
+                        for k in ("center", "pixel00", "du", "dv"):
+                            getattr(view, k)[:] = [float(x) for x in v[k]]
+                        view.width, view.height = int(v["width"]), int(v["height"])
+                    keep.append(view)
+                    a = C.byref(view)
+            elif kind == "reuse":
+                a = None if has else self.ones.ctypes.data
+            elif kind == "cam":
+                a = None if has else self.cam._h
+            elif kind == "prev_cam":
+                a = self.other._h if v == "other" else None if has else self.prev._h
+            elif kind == "hist":
+                a = None if has else self.hist._h
+            else:  # opt, out, opt_hist
+                a = self.hist._h if v == "hist" else None
+            args.append(a)
+        code = getattr(lib, entry)(*args)
+        return int(code), lib.rt_last_error().decode("utf-8", "replace")
+
+
+# ---- rows that need an open session (a GPU) ---------------------------------------------------------
+def session_cases():
+    """[(id, env, entry, overrides)] - env "bounces": a mode-bounces camera, "radiance": the default
+    mode; both with a session at samples_done 1. h "hist": an empty history, "region": a history
+    committed by another camera's session over the region (0, 0, 8, 8)."""
+    two = {"levels": 9, "sigma_plane": "-0.5"}
+    var, hsrc = {"source": 0}, {"source": 2}
+    return [
+        ("plain filter, bounces + levels=9: the mode", "bounces", "rt_camera_progressive_denoise", {"options": two}),
+        ("variance-guided filter, bounces + levels=9: the options", "bounces", "rt_camera_progressive_denoise_variance",
+         {"options": two}),
+        ("variance-guided filter at 1 sample", "radiance", "rt_camera_progressive_denoise_variance", {}),
+        ("variance at 1 sample", "radiance", "rt_camera_progressive_variance", {}),
+        ("accumulated at 1 sample", "radiance", "rt_camera_progressive_accumulate", {}),
+        ("focus on the variance at 1 sample", "radiance", FOCUS, {"options": var}),
+        ("reprojected, sigma_plane=nan + different scenes", "radiance", "rt_camera_progressive_reproject",
+         {"options": {"sigma_plane": "nan"}, "prev_cam": "other"}),
+        ("focus on an empty history", "radiance", FOCUS, {"options": hsrc, "h": "hist"}),
+        ("focus on a history of another region", "radiance", FOCUS, {"options": hsrc, "h": "region"}),
+    ]
+
+
+class SessionEnv:
+    """Env per camera mode with one step(1) done, and the history of another region."""
+
+    def __init__(self, rt):
+        self.envs = {"radiance": Env(rt), "bounces": Env(rt, {**RO, "mode": "bounces"})}
+        self.sessions = [e.cam.progressive() for e in self.envs.values()]
+        for s in self.sessions:
+            s.step(1)
+        self.region_hist = rt.History()
+        with self.envs["radiance"].prev.progressive((0, 0, 8, 8)) as pr:
+            pr.step(2)
+            pr.accumulated(self.region_hist)
+
+    def call(self, env, entry, ov):
+        e = self.envs[env]
+        if ov.get("h") == "region":
+            keep, e.hist = e.hist, self.region_hist
+            try:
+                return e.call(entry, {**ov, "h": "hist"})
+            finally:
+                e.hist = keep
+        return e.call(entry, ov)
+
+    def close(self):
+        for s in self.sessions:
+            s.close()

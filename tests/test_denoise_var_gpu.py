@@ -212,6 +212,28 @@ def test_filter_of_a_synthetic_frame_with_non_finite_pixels(rt, gpu):
     assert np.isfinite(vout).all() and (vout >= 0).all()
 
 
+def test_each_output_alone_is_the_all_outputs_call_on_the_synthetic_frame(rt, gpu):
+    """The raw entry with one output pointer at a time over a region off the tile grid: every
+    single output equals, bit for bit, the same output of the call that asks for all three."""
+    import pass_error_cases as pc
+    c, var, n, P, dist, obj = synthetic_frame()
+    H, W = obj.shape
+    region = (3, 5, 29, 15)
+    env = pc.Env(rt)
+    base = dict(width=W, height=H, region=region, options={"levels": 3, "sigma_variance": 0.7, "sigma_plane": 0.05},
+                radiance=c, variance=var, normal=n, position=P, distance=np.ascontiguousarray(dist), object=obj)
+    new = lambda: {"radiance_out": np.full((H, W, 3), -123.25, np.float32),   # noqa: E731
+                   "variance_out": np.full((H, W), -123.25, np.float32), "rgb_out": np.full((H, W, 3), 0xA5, np.uint8)}
+    full = new()
+    assert env.call("rt_denoise_variance", {**base, **full})[0] == 0
+    box, _ = _box(region, H, W)
+    assert all((a[box] != new()[k][box]).any() for k, a in full.items())
+    for k in full:
+        one = new()
+        assert env.call("rt_denoise_variance", {**base, k: one[k]})[0] == 0, k
+        assert bits_equal(one[k], full[k]).all(), k
+
+
 def test_filter_of_a_synthetic_frame_wider_than_a_row_group(rt, gpu):
     """70x21: the global kernel (step 4) covers 64 pixels of 4 rows per workgroup, so 70 crosses
     its row group and the 16-pixel tiles with a ragged edge, 21 its 4 rows and a tile. The

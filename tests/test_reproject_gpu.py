@@ -154,6 +154,34 @@ def test_explicit_buffers_on_a_synthetic_pair_of_views(rt, gpu, opts, counts):
     assert bits_equal(h2[box], hist[box]).all() and (h2[_box(REGION, *NEW_SHAPE)[1]] == 0).all()
 
 
+def test_each_output_alone_is_the_all_outputs_call_on_the_synthetic_pair(rt, gpu):
+    """The raw entry with one output pointer at a time (the outputs gate which unpack passes run):
+    every single output equals, bit for bit, the same output of the call that asks for all four."""
+    import pass_error_cases as pc
+    view, g, pview, pg, prad, fresh, pxs, reusable = synthetic()
+    H, W = NEW_SHAPE
+    env = pc.Env(rt)
+    base = dict(width=W, height=H, region=REGION, **g, prev_view=pview, prev_region=PREV_REGION, prev_radiance=prad,
+                **{"prev_" + k: v for k, v in pg.items()}, reusable=reusable, n_objects=len(reusable), radiance=fresh,
+                px_samples=pxs, samples=0)
+    new = lambda: {"history_out": np.full((H, W, 3), SENT, F), "weight_out": np.full((H, W), SENT, F),   # noqa: E731
+                   "radiance_out": np.full((H, W, 3), SENT, F), "rgb_out": np.full((H, W, 3), 0xA5, np.uint8)}
+    full = new()
+    assert env.call("rt_reproject", {**base, **full})[0] == 0
+    box, _ = _box(REGION, H, W)
+    assert all((a[box] != new()[k][box]).any() for k, a in full.items())
+    for k in full:
+        one = new()
+        assert env.call("rt_reproject", {**base, k: one[k]})[0] == 0, k
+        assert bits_equal(one[k], full[k]).all(), k
+    # history only (no fresh frame): the history and the weight, alone and together
+    hist_only = {k: v for k, v in base.items() if k not in ("radiance", "px_samples")}
+    for keys in (("history_out",), ("weight_out",), ("history_out", "weight_out")):
+        one = new()
+        assert env.call("rt_reproject", {**hist_only, **{k: one[k] for k in keys}})[0] == 0, keys
+        assert all(bits_equal(one[k], full[k]).all() for k in keys), keys
+
+
 # ---- 2. the camera entry ---------------------------------------------------------------------------
 CAMERA_CASES = {
     "cornell40": ({"type": "cornell"}, {"width": 40, "samples": 8, "depth": 8, "aTolerance": 0}, "brute"),

@@ -172,6 +172,30 @@ def test_explicit_buffers_on_synthetic_pairs_of_views(rt, gpu, pair, opts, count
         assert bits_equal(plain["length"], want["length"]).all() and bits_equal(plain["weight"], want["weight"]).all()
 
 
+@pytest.mark.parametrize("levels", [0, 2], ids=["unfiltered", "filter2"])
+def test_each_output_alone_is_the_all_outputs_call_on_the_small_pair(rt, gpu, levels):
+    """The raw entry with one output pointer at a time (the outputs gate the filter and which
+    unpack passes run): every single output equals, bit for bit, the same output of the call that
+    asks for all five."""
+    import pass_error_cases as pc
+    region, g, hist, fresh, pxs, var, reusable = synthetic("small")
+    H, W = pxs.shape
+    env = pc.Env(rt)
+    base = dict(width=W, height=H, region=region, **g, radiance=fresh, px_samples=pxs, samples=0, variance=var,
+                prev_view=hist["view"], prev_region=hist["region"], **{"prev_" + k: v for k, v in hist["guides"].items()},
+                prev_radiance=hist["radiance"], prev_variance=hist["variance"], prev_length=hist["length"],
+                reusable=reusable, n_objects=len(reusable), options={"filter_levels": levels})
+    new = lambda: {k + "_out": v for k, v in sentinels(H, W).items()}   # noqa: E731
+    full = new()
+    assert env.call("rt_temporal_accumulate", {**base, **full})[0] == 0
+    box, _ = _box(region, H, W)
+    assert all((a[box] != new()[k][box]).any() for k, a in full.items())
+    for k in full:
+        one = new()
+        assert env.call("rt_temporal_accumulate", {**base, k: one[k]})[0] == 0, k
+        assert bits_equal(one[k], full[k]).all(), (k, levels)
+
+
 # ---- 2. the session entry ------------------------------------------------------------------------------
 SESSION_CASES = {
     "cornell40": ({"type": "cornell"}, {"width": 40, "samples": 60, "depth": 8}, "brute"),
