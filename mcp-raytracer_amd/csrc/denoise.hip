@@ -8,6 +8,9 @@
 
 #include <algorithm>
 
+#include "pt_pixel.hpp"  // item_pixel
+#include "pt_shade.hpp"  // pixel_center, closest_hit_any
+
 namespace rt {
 
 // ---- guide pass -------------------------------------------------------------------------------

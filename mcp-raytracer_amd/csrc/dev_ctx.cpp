@@ -245,7 +245,7 @@ void DevCtx::launch(const rt_region& region, int tile_group, int tile_groups, in
     S.lds_node_pad = plan.node_pad;
     S.n_top = plan.n_top;
     // trees walked from global memory: leaf records that carry the exact test's fp64 radius
-    // (the LDSS-0 chunked kernels read them, pt_kernel.hpp leaf_test L2)
+    // (the LDSS-0 chunked kernels read them, pt_walk.hpp leaf_test L2)
     S.tsph2 = blob.off_tsph2 >= 0 ? reinterpret_cast<const RtLeafSph*>(reinterpret_cast<const char*>(d_blob.p) + blob.off_tsph2)
                                   : nullptr;
     if (g.lds_level == 0 && r.v.trav == TRAV_FAST && !S.tsph2 && C.n_prims > 0)

@@ -1,13 +1,15 @@
 // Kernel launch entry points, one translation unit per scalar precision so the
 // ref build can be compiled with -ffp-contract=off (no fused multiply-adds:
 // the reference's JS arithmetic never fuses) while the fp32 build may fuse.
+// Host side only: the kernels' headers (pt_num.hpp ... pt_dispatch.hpp) are included by the
+// .hip units that instantiate them.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "pt_kernel.hpp"
+#include "pt_types.hpp"
 
 namespace rt {
 
@@ -71,74 +73,13 @@ hipError_t launch_tiles_unpack(const void* slabs, int groups, int slab_tiles, co
 // LDS bytes per workgroup for the traversal stack (fast / reference) or the
 // per-lane candidate bounds of the nearest-first brute force.
 // `lds_tree`: the launch's tree is LDS-resident (LDSS > 0), whose fast-walk stack entries are 16-bit
-// (StackT, pt_kernel.hpp)
+// (StackT, pt_types.hpp)
 inline size_t stack_lds_bytes(int stack_depth, int trav, int n_prims, bool lds_tree = false) {
     if (trav == TRAV_BRUTE)  // larger forced brute-force scenes take the in-order loop (no LDS)
         return n_prims <= kBruteMaxPrims ? (size_t)std::max(n_prims, 1) * kStackStride * sizeof(uint16_t) : 0;
     const size_t d = (size_t)(stack_depth > 0 ? stack_depth : 1);
     const size_t e = lds_tree ? sizeof(StackT<1>) : sizeof(StackT<0>);
     return d * kStackStride * e;
-}
-
-// The kernel template instance of a launch (one per scalar precision unit: pt_ref.hip,
-// pt_fp32.hip). sb == nullptr: the sequential-pixel kernel; else the chunked kernel, or the
-// pool kernel (product brute-force builds; RT_POOL_PROF adds its ref-precision timer build).
-template <class Real, bool EMIT, int INSTR, int TRAV, int LDSS>
-hipError_t dispatch_kernel(const DevScene& S, const RtRegion& reg, const RenderOut& out, const LaunchGeom& g,
-                           const SampleBuf* sb, bool pool, const uint2* ptab, hipStream_t stream) {
-    if (sb && pool) {
-        if constexpr (!EMIT && TRAV == TRAV_BRUTE && (INSTR == 0 || (RT_POOL_PROF && INSTR == 2 && sizeof(Real) == 8))) {
-            if (ptab)  // with the primary-ray candidate table (primary.hpp)
-                hipLaunchKernelGGL((pt_pool_primary_kernel<Real, TRAV, LDSS>), dim3(g.grid), dim3(kBlockPool),
-                                   g.lds_bytes, stream, S, reg, out, g.tiles_x, *sb, ptab);
-            else
-                hipLaunchKernelGGL((pt_pool_kernel<Real, TRAV, LDSS>), dim3(g.grid), dim3(kBlockPool), g.lds_bytes,
-                                   stream, S, reg, out, g.tiles_x, *sb);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    if (sb)
-        hipLaunchKernelGGL((pt_chunk_kernel<Real, EMIT, INSTR, TRAV, LDSS>), dim3(g.grid), dim3(kBlockChunk),
-                           g.lds_bytes, stream, S, reg, out, g.tiles_x, *sb);
-    else
-        hipLaunchKernelGGL((pt_render_kernel<Real, EMIT, INSTR, TRAV, LDSS>), dim3(g.grid), dim3(kBlock), g.lds_bytes,
-                           stream, S, reg, out, g.tiles_x, g.my_tiles);
-    return hipGetLastError();
-}
-
-template <class Real, bool EMIT, int INSTR, int TRAV>
-hipError_t dispatch_level(const DevScene& S, const RtRegion& reg, const RenderOut& out, const LaunchGeom& g,
-                          const SampleBuf* sb, bool pool, const uint2* ptab, hipStream_t stream) {
-    // LDS residency levels (pt_kernel.hpp scene_prologue); never with the reference traversal
-    constexpr int L1 = trav_fast(TRAV) ? 1 : 0, L2 = TRAV == TRAV_REFERENCE ? 0 : 2;
-    if (g.lds_level >= 2) return dispatch_kernel<Real, EMIT, INSTR, TRAV, L2>(S, reg, out, g, sb, pool, ptab, stream);
-    if (g.lds_level == 1) return dispatch_kernel<Real, EMIT, INSTR, TRAV, L1>(S, reg, out, g, sb, pool, ptab, stream);
-    return dispatch_kernel<Real, EMIT, INSTR, TRAV, 0>(S, reg, out, g, sb, pool, ptab, stream);
-}
-
-template <class Real, int TRAV>
-hipError_t dispatch_variant(const KernelVariant& v, const DevScene& S, const RtRegion& reg, const RenderOut& out,
-                            const LaunchGeom& g, const SampleBuf* sb, hipStream_t stream) {
-    if (v.count == 2)
-        return v.emit ? dispatch_level<Real, true, 2, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream)
-                      : dispatch_level<Real, false, 2, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream);
-    if (v.count == 1)
-        return v.emit ? dispatch_level<Real, true, 1, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream)
-                      : dispatch_level<Real, false, 1, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream);
-    return v.emit ? dispatch_level<Real, true, 0, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream)
-                  : dispatch_level<Real, false, 0, TRAV>(S, reg, out, g, sb, v.pool, v.ptab, stream);
-}
-
-template <class Real>
-hipError_t dispatch_render(const KernelVariant& v, const DevScene& S, const RtRegion& reg, const RenderOut& out,
-                           const LaunchGeom& g, const SampleBuf* sb, hipStream_t stream) {
-    if (v.trav == TRAV_BRUTE) return dispatch_variant<Real, TRAV_BRUTE>(v, S, reg, out, g, sb, stream);
-    if (v.trav == TRAV_FAST)
-        return v.defer ? dispatch_variant<Real, TRAV_FAST_DEFER>(v, S, reg, out, g, sb, stream)
-                       : dispatch_variant<Real, TRAV_FAST>(v, S, reg, out, g, sb, stream);
-    return dispatch_variant<Real, TRAV_REFERENCE>(v, S, reg, out, g, sb, stream);
 }
 
 }  // namespace rt

@@ -1,4 +1,4 @@
-// Launch planning (launch_plan.hpp). Compiled like the ABI units (it reads pt_kernel.hpp's
+// Launch planning (launch_plan.hpp). Compiled like the ABI units (it reads pt_types.hpp's
 // constants and SampleBuf) but calls nothing of the HIP runtime.
 #include "launch_plan.hpp"
 
@@ -110,7 +110,7 @@ LaunchPlan plan_launch(const CamHost& host, const SceneBlob& blob, int cus, int 
     // records through scalar loads either way; LDS serves the per-lane
     // reads (hit record, materials, light sampling).
     const size_t lds_cap = (size_t)std::min(lds_max, kLdsSceneMaxBytes);
-    // the LDS copy pads every 4-wide node to 144 bytes (pt_kernel.hpp t4_node: LDS bank windows)
+    // the LDS copy pads every 4-wide node to 144 bytes (pt_walk.hpp t4_node: LDS bank windows)
     const int32_t node_pad =
         v.trav == TRAV_FAST && env_flag("RT_AMD_NODE_PAD", true) ? (int32_t)build.t4nodes.size() : 0;
     g.lds_level = 0;

@@ -7,7 +7,7 @@
 // each one's t; for the primary rays of one pixel that answer is nearly the same for every
 // sample. primary_record() computes it ONCE per pixel, conservatively for the pixel's whole
 // footprint, in double interval arithmetic; the pool kernel's primary-ray trips read the
-// record and go straight to the exact tests (pt_kernel.hpp closest_hit_primary). The exact
+// record and go straight to the exact tests (pt_brute.hpp closest_hit_primary). The exact
 // pass takes the lexicographic minimum of (t, slot) over the candidates it tests, so any
 // superset of the true candidates with valid lower bounds returns the same hit.
 //
@@ -34,8 +34,8 @@
 namespace rt {
 
 constexpr int kPrimaryMaxPrims = 16;          // = kBruteMaxPrims: one mask bit per primitive
-constexpr double kPrimRel = 1e-5;             // pt_kernel.hpp kRel
-constexpr double kPrimTmin = 0.001 * (1.0 - 1e-5);  // pt_kernel.hpp kTminLo
+constexpr double kPrimRel = 1e-5;             // pt_isect.hpp kRel
+constexpr double kPrimTmin = 0.001 * (1.0 - 1e-5);  // pt_isect.hpp kTminLo
 
 // Closed interval [lo, hi] of doubles. Outward rounding is not applied per operation: the
 // double roundings (2^-53 relative) are ~2^-29 of the kRel margins every decision carries.
@@ -169,7 +169,7 @@ RT_HD bool primary_candidate(const RtPrim& p, const double* o, const PIv* d, dou
 
 // Pixel (i, j)'s record. `prims` in slot order, n_prims <= kPrimaryMaxPrims.
 RT_HD uint64_t primary_record(const RtCamera& C, const RtPrim* prims, int n_prims, int i, int j) {
-    // pixel_center's fp32 operations (pt_kernel.hpp); the box below is widened for their
+    // pixel_center's fp32 operations (pt_shade.hpp); the box below is widened for their
     // rounding anyway, so the value need not be the kernel's in every bit
     double o[3];
     PIv d[3];

@@ -12,7 +12,7 @@
 
 namespace rt {
 
-// = sizeof(ProgPix) (progressive.hpp), kTile and kWave (pt_kernel.hpp); dev_ctx.cpp asserts them
+// = sizeof(ProgPix) (progressive.hpp), kTile and kWave (pt_types.hpp); dev_ctx.cpp asserts them
 constexpr size_t kProgPixBytes = 48;
 constexpr int kProgTile = 8, kProgWave = 64;
 

@@ -5,6 +5,8 @@
 
 #include <algorithm>
 
+#include "pt_pixel.hpp"
+
 namespace rt {
 
 constexpr int kProgBlock = 256;

@@ -1,6 +1,6 @@
 // fp32 fast-mode build of the path tracer (Real = float). Same algorithm and
 // draw order as the ref build; parity with the ref oracle is tolerance-based.
-#include "launch.hpp"
+#include "pt_dispatch.hpp"
 
 namespace rt {
 

@@ -1,7 +1,7 @@
 // Reference-precision build of the path tracer (Real = double, fp32 vector
 // stores). Compiled with -ffp-contract=off so every scalar op rounds exactly as
 // the reference's JS doubles do.
-#include "launch.hpp"
+#include "pt_dispatch.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void world_hit_kernel(DevScene S, int n, co
 }
 
 // The device's Math.cos / Math.sin of the cosine-PDF angle and Schlick's
-// Math.pow(x, 5), with the path code's own expressions (pt_kernel.hpp path_post,
+// Math.pow(x, 5), with the path code's own expressions (pt_shade.hpp path_post,
 // dielectric_dir): phi = 2 * PI * xi, xi = u * 2^-32.
 __global__ void math_probe_kernel(int n, const uint32_t* u, double* out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;

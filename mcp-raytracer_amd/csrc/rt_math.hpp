@@ -197,7 +197,7 @@ RT_HD Real js_max(Real a, Real b) {
 template <class Real>
 RT_HD V3 ray_at(V3 o, V3 d, Real t) { return add(o, scale<Real>(d, t)); }
 
-// splitmix64 finaliser (seeds the per-path PCG32 streams, pt_kernel.hpp rng_init).
+// splitmix64 finaliser (seeds the per-path PCG32 streams, pt_num.hpp rng_init).
 RT_HD uint64_t splitmix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -684,7 +684,7 @@ struct Builder {
     // quad.ts:400-422); Sphere ctor (sphere.ts:20-31).
     // Axis-aligned quad (u, v each along one axis): the kernel evaluates the
     // reference's Plane.intersect / alpha / beta with the zero terms dropped,
-    // which rounds identically (pt_kernel.hpp aquad_t). Encoding:
+    // which rounds identically (pt_isect.hpp aquad_t). Encoding:
     //   g4[3] = int code 1 + a + 3*vflag (a = normal axis; vflag: v along (a+2)%3),
     //   g3[3] = +-w[a] (sign folded from the cross product), g2[3] = v's nonzero
     //   component, g1[3] = u's nonzero component. code 0 = general quad.
@@ -750,7 +750,7 @@ struct Builder {
             p.g3[0] = n.x; p.g3[1] = n.y; p.g3[2] = n.z;
             p.g4[0] = w.x; p.g4[1] = w.y; p.g4[2] = w.z;
             // general quads: |w||u|, |w||v| (rounded up) scale the kernel's alpha/beta
-            // error margins (pt_kernel.hpp planar_maybe); axis quads re-use the slots
+            // error margins (pt_walk.hpp planar_maybe); axis quads re-use the slots
             {
                 const double wn = std::sqrt(len2<double>(w));
                 p.g1[3] = (float)(wn * std::sqrt(len2<double>(u)) * (1.0 + 1e-5));
@@ -878,7 +878,7 @@ int32_t loop_threshold(double x) {
 
 }  // namespace
 
-// Boxes for the fast traversal (pt_kernel.hpp closest_hit_fast). The
+// Boxes for the fast traversal (pt_walk.hpp closest_hit_fast). The
 // reference's AABB.hit never accepts a box that is inverted or flat on an
 // axis (its per-axis interval is empty), and always accepts one with a NaN
 // bound; a strict slab test would treat those differently, so they are
@@ -989,7 +989,7 @@ static int32_t t4_build(const std::vector<RtNode>& f, int32_t i, int depth, std:
 }
 // The 4-wide nodes re-numbered breadth-first (root 0, then its children, ...): any prefix of
 // the array is the top of the tree - the nodes every ray's walk starts with - which a launch
-// walking the tree from global memory copies into LDS (pt_kernel.hpp t4_node). The walk's
+// walking the tree from global memory copies into LDS (pt_walk.hpp t4_node). The walk's
 // result does not depend on node numbering (the (t, slot) minimum).
 static std::vector<RtT4Node> t4_breadth_first(const std::vector<RtT4Node>& in) {
     std::vector<int32_t> order, idx(in.size(), -1);
@@ -1043,7 +1043,7 @@ struct SahBuilder {
     // the cost rule may keep, and the size below which a node is always a leaf (defaults 1, 4, 2;
     // RT_AMD_SAH_CT / RT_AMD_SAH_MAXLEAF / RT_AMD_SAH_FORCELEAF override, for A/B)
     // One primitive per leaf where the walk tests a leaf's primitives exactly as it reaches them
-    // (no deferred exact tests, pt_kernel.hpp leaf_test): trees too large for the LDS-resident copy
+    // (no deferred exact tests, pt_walk.hpp leaf_test): trees too large for the LDS-resident copy
     // (> 1,024 primitives: every leaf costs an L2 round trip for its records and its pre-filter loop
     // runs at the lanes that hold it; spheres-100k 2048^2 spp16 with the fp64 leaf records: leaves
     // <= 4: 33.6 ms, <= 2: 32.1, 1: 30.1) and small ones (< 100 primitives; rain-50 1080p spp128:
@@ -1400,7 +1400,7 @@ SceneBuild build_scene(const Value& scene_data, const Value* render_options) {
         }
     }
     // stack entries: reference DFS (depth + 1), binary fast tree (depth + 1),
-    // 4-wide tree (up to 3 pushes per level + 1). The 4-wide node step (pt_kernel.hpp t4_step)
+    // 4-wide tree (up to 3 pushes per level + 1). The 4-wide node step (pt_walk.hpp t4_step)
     // writes up to sp + 2 whatever it pushes: at a node of level L the stack holds at most
     // 3 (L - 1) entries, so its writes stay below 3 t4depth entries - inside this bound.
     cam.stack_depth = std::max(b.out.bvh_depth, 3 * b.out.t4depth + 1) + 1;

@@ -113,7 +113,7 @@ std::vector<RtPre> prefilter_records(const std::vector<RtPrim>& prims, int32_t* 
             q.f[2] = (float)asu;
             q.f[3] = (float)(-(double)p.g0[ia] * asv - 0.5);  // alpha - 1/2 at the quad's corner
             q.f[4] = (float)(-(double)p.g0[ib] * asu - 0.5);
-            constexpr double kRelPre = 1e-5;  // pt_kernel.hpp kRel
+            constexpr double kRelPre = 1e-5;  // pt_isect.hpp kRel
             q.f[5] = (float)(kRelPre * std::max(std::fabs((double)p.g0[ia]), std::fabs((double)p.g0[ib])) * (1.0 + 1e-6));
         } else {
             q.kind = PRE_OTHER;

@@ -14,7 +14,7 @@
 
 namespace rt {
 
-// = pt_kernel.hpp kBruteMaxPrims (launch_plan.cpp asserts it): larger scenes carry no exact /
+// = pt_types.hpp kBruteMaxPrims (launch_plan.cpp asserts it): larger scenes carry no exact /
 // pre-filter records, only closest_hit_brute_nf reads them
 constexpr int kBlobBruteMaxPrims = 16;
 

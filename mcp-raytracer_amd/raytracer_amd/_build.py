@@ -66,7 +66,8 @@ _UNITS = [
     ("primary.hip", ["-ffp-contract=off"], True),
     ("frame.hip", [], True),
     ("png.hip", [], True),
-    # the C ABI and the host side of a launch: compiled as HIP for pt_kernel.hpp's types
+    # the C ABI and the host side of a launch: compiled as HIP for the vector types (float4, uint2, ...)
+    # in pt_types.hpp's launch structs and the launch declarations; it sees no device code but rt_math.hpp's
     ("rt_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     # the frame passes' ABI units, with rt_api.cpp's flags: reproject.hpp's rp_view_constants and
     # dn_filter's per-level scalar are host computations that must not be contracted
@@ -84,7 +85,9 @@ _UNITS = [
     ("prog_blob.cpp", ["-ffp-contract=off"], False),
     ("image.cpp", [], False),
 ]
-_HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_kernel.hpp", "launch.hpp", "progressive.hpp", "denoise.hpp",
+_HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
+            "pt_brute.hpp", "pt_shade.hpp", "pt_pixel.hpp", "pt_kernels.hpp", "pt_pool.hpp", "pt_dispatch.hpp",
+            "launch.hpp", "progressive.hpp", "denoise.hpp",
             "reproject.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp", "api_call.hpp", "pass_host.hpp"]
 _LIBS = ["-lz"]

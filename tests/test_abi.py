@@ -60,7 +60,7 @@ def test_pool_kernel_trip_loop_waits_on_no_stores(rt, tmp_path):
     prologue's and the work hand-out's few: a vmcnt(0) in the trip loop also waits for the sample
     records stored just before it. Round 6 found 17 such waits, inserted before writes of a register
     the wait-count pass kept pending from the adaptive active-list load on the paths around its
-    branch (pt_kernel.hpp slot_pixel; Cornell +0.4 %, fp32 +1.3 %, adaptive +4 %)."""
+    branch (pt_pixel.hpp slot_pixel; Cornell +0.4 %, fp32 +1.3 %, adaptive +4 %)."""
     import shutil
     import subprocess
     import sys

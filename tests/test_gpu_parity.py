@@ -509,7 +509,7 @@ def test_prefilter_pair_records_match_oracle(rt, oracle, gpu):
                          ids=["cornell", "spheres500", "spheres6000"])
 def test_near_parallel_rays_match_oracle(rt, oracle, gpu, cfg):
     """make_fray leaves an axis with 0 < |d_a| < 1e-3 max|d| out of the slab test's
-    absolute slack (pt_kernel.hpp make_fray): rays whose components are +-1e-4, 1e-6 and 1e-9
+    absolute slack (pt_walk.hpp make_fray): rays whose components are +-1e-4, 1e-6 and 1e-9
     times max|d| on one or two axes, from origins at |o| = 10 .. 1e4 aimed at the scene, through
     the fast walk (and brute force) against the reference-order traversal and the oracle."""
     sd = rt.generate_scene_data(cfg)
@@ -614,7 +614,7 @@ def test_pool_kernel_equals_chunked_kernel(rt, gpu, case, monkeypatch):
 ])
 def test_pool_host_gates_fall_back_bit_exact(rt, oracle, gpu, ro, kernel):
     """The pool kernel packs the bounce phase into 8 bits and the sample index
-    into 16 (pt_kernel.hpp pool_meta / pool_hs); launch_plan.cpp gates it on
+    into 16 (pt_pool.hpp pool_meta / pool_hs); launch_plan.cpp gates it on
     depth <= 250 and spp <= 65535. On each side of both gates the default path
     picks the expected kernel and matches the oracle bit for bit."""
     sd = rt.generate_scene_data({"type": "cornell"})

@@ -1,4 +1,4 @@
-"""The pool kernel's trips (pt_kernel.hpp pool_trips): a front stage (path start, diffuse
+"""The pool kernel's trips (pt_pool.hpp pool_trips): a front stage (path start, diffuse
 shading, or none for a specular continuation) followed by the common back stage that traces the
 path's next ray. Every case renders on the pool kernel, on the chunked kernel of the same build
 and on the oracle, with and without the primary-ray table, and compares u8, fp32 radiance bit

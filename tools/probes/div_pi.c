@@ -1,4 +1,4 @@
-/* Host check of the kernel's div_pi (pt_kernel.hpp): RN(x/PI) == fma-corrected RN(x*RN(1/PI)) on 4e8 doubles in (0,1]. gcc -O2 -ffp-contract=off div_pi.c -lm */
+/* Host check of the kernel's div_pi (pt_shade.hpp): RN(x/PI) == fma-corrected RN(x*RN(1/PI)) on 4e8 doubles in (0,1]. gcc -O2 -ffp-contract=off div_pi.c -lm */
 #include <stdio.h>
 #include <math.h>
 #include <stdint.h>

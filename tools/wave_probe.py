@@ -5,7 +5,7 @@ Needs the diagnostic variant library built from a tree with tools/wave_probe.pat
 (the probe is not in the product kernel) and RT_WAVE_PROBE=1 (run with
 RT_AMD_VARIANT=<its name>): every wave of a chunked / pool launch records the 100 MHz real-time
 clock at its start, when the item hand-out ran dry for it, and at its end, plus its item count
-and hardware ids (pt_kernel.hpp WaveProbe). For each scene and tile-group count N it renders
+and hardware ids (WaveProbe, which tools/wave_probe.patch adds to the kernels). For each scene and tile-group count N it renders
 tile group 0 of N (rank 0's share under bench.py --gpus N, as tools/rank_share.py) and prints
 the launch span, the percentiles of the waves' dry and end times, the drain (end - dry) and the
 last waves.
@@ -26,7 +26,7 @@ sys.path.insert(0, str(ROOT))
 EXTRA = {"cornell": {"width": 800, "samples": 256, "depth": 16},
          "spheres": {"width": 800, "samples": 64, "depth": 8},
          "rain": {"width": 1920, "samples": 512, "depth": 16}}
-SLOTS = 8192  # pt_kernel.hpp kWaveProbeSlots
+SLOTS = 8192  # kWaveProbeSlots of tools/wave_probe.patch
 TICK_US = 0.01  # s_memrealtime: 100 MHz
 
 
