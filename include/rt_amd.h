@@ -568,6 +568,54 @@ int rt_camera_denoise_variance(rt_camera* cam, const rt_region* region, const rt
 int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_options* options, uint8_t* rgb,
                                            float* radiance, float* variance_out);
 
+/* ---- Guides through mirrors and glass ----------------------------------------------------------
+ * Opt-in like the blocks above: no other call changes. The first-hit guides report a mirror's or
+ * a glass ball's own surface; these follow the pixel's specular chain to the first surface that
+ * is not specular, so the filter sees the edges of what is reflected or seen through.
+ * tests/guide_walk_ref.py is the normative definition; in words:
+ *
+ * A deterministic walk per pixel, no RNG, always ref precision, through the camera's traversal.
+ * State: a ray, an fp32 dist = 0, k = 0. Segment 0 is the first-hit guides' pinhole ray. Loop:
+ * take the ray's closest hit on (0.001, inf). A miss ends the walk: with k == 0 the pixel is a
+ * miss (zeros, object -1, end code 0), else the guide is the specular surface the chain left
+ * through last (end code 2). On a hit, position, the normal facing the ray and the face are the
+ * first-hit guides'; dist += sqrtf((qx qx + qy qy) + qz qz) of q = position - origin in fp32, in
+ * segment order; cur = (normal, position, dist, object). The hit's material is then resolved as
+ * Material.scatter resolves it, with a policy in place of every random draw:
+ *   lambert, light, no material  terminal
+ *   metal     f = reflect(unit(d), n); terminal when fuzz > max_fuzz or f.n <= 0; else continue
+ *             along f (the fuzz term is dropped)
+ *   glass     the dielectric's arithmetic without its draw: refract whenever ratio sinT <= 1,
+ *             else reflect (Schlick's reflectance is ignored); always continues
+ *   mixed     the child `diff` when its weight >= 0.5, else `spec`
+ *   layered   the outer dielectric by the glass rule; a reflection continues; a refraction
+ *             becomes the incoming direction of the inner material at the same hit
+ * A terminal material ends the walk with cur (end code 1); k == max_bounces ends it with cur
+ * (end code 3); otherwise the walk continues from the position along the new direction, k += 1.
+ * Outputs: the four guide arrays of rt_camera_render_guides, and chain (int32) = k | end << 8.
+ * A scene without specular materials gives the first-hit guides in every bit, chain = 1 << 8 on
+ * every hit.
+ *
+ * rt_camera_render_guides_ex: any output may be NULL; options NULL = rt_guide_options_default
+ * (first hit, 8, 0). Mode RT_GUIDES_FIRST_HIT is rt_camera_render_guides, chain = hit ? 1 << 8 : 0.
+ * rt_camera_set_denoise_guides selects the guides the four camera filter calls compute
+ * (rt_camera_denoise, rt_camera_denoise_variance, rt_camera_progressive_denoise,
+ * rt_camera_progressive_denoise_variance); NULL, or never calling it, means first hit. A session
+ * keeps its specular guides beside its first-hit ones, recomputed when the options change;
+ * reprojection, accumulation and focus always use first-hit guides. rt_camera_denoise_times'
+ * guide_ms covers whichever pass ran. RT_ERR_INVALID, decided before any device call: an unknown
+ * mode, max_bounces outside 1..64, a negative or non-finite max_fuzz.
+ * Limits: one deterministic branch per interface (no Schlick split), fuzzy metals above max_fuzz
+ * are terminal, a defocused camera's blur is not in the guides, and reprojection and the view
+ * history still stop at specular surfaces. Not in the N-API addon or the multi-GPU render. */
+enum { RT_GUIDES_FIRST_HIT = 0, RT_GUIDES_SPECULAR = 1 };
+typedef struct { int32_t mode; int32_t max_bounces; float max_fuzz; } rt_guide_options;
+void rt_guide_options_default(rt_guide_options* options);
+int rt_camera_render_guides_ex(rt_camera* cam, const rt_region* region, const rt_guide_options* options, float* normal,
+                               float* position, float* distance, int32_t* object, int32_t* chain);
+int rt_camera_set_denoise_guides(rt_camera* cam, const rt_guide_options* options);
+int rt_camera_get_denoise_guides(rt_camera* cam, rt_guide_options* options);
+
 /* ---- Reprojection of a previous view's frame into a new camera view --------------------------
  * No reference counterpart (the reference renders every frame from scratch). Opt-in like the two
  * blocks above: no other call changes.

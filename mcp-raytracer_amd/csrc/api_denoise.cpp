@@ -1,5 +1,6 @@
 // C ABI of the guides and the a-trous filter (denoise.hpp), plain and variance-guided: the guide
-// render, the three shapes of a filter call, the session's variance and the filter's timings.
+// render (first hit, or through the specular chain) and the guides a camera's filter calls compute,
+// the three shapes of a filter call, the session's variance and the filter's timings.
 #include "pass_host.hpp"
 
 using namespace rt;
@@ -80,7 +81,7 @@ static int dn_camera_call(rt_camera* cam, const std::string& who, DnOpts o, cons
             io.up(b.var, variance, sizeof(float));
         }
         hip_check(hipEventRecord(ev[0], io.stream), "hipEventRecord");
-        c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{b.gn, b.gp}, io.stream);
+        c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{b.gn, b.gp}, io.stream, &cam->dn_guide);
         c.dn_guides = true;
         dn_filter(b, b.gn, b.gp, b.rad(), io.r.width, 0, 0, io.r.width, io.r.height, o, radiance_out != nullptr,
                   rgb_out != nullptr, variance_out != nullptr, io.stream, ev + 1);
@@ -106,14 +107,42 @@ static int dn_session_call(rt_camera* cam, const std::string& who, DnOpts o, uin
         b.ensure((size_t)io.n());
         hipEvent_t* ev = c.dn_events(o.levels);
         hip_check(hipEventRecord(ev[0], io.stream), "hipEventRecord");
-        // the span [0, 1): the guide pass of a first call and, variance-guided, the variance pass
-        c.dn_guides = o.var || !P.d_gn;
-        session_guides(cam, c, io.stream);
+        // the span [0, 1): the guide pass of a first call (through the specular chain: of the first
+        // call with these options) and, variance-guided, the variance pass
+        const bool spec = cam->dn_guide.mode == RT_GUIDES_SPECULAR;
+        c.dn_guides = o.var || (spec ? !session_specular_cached(c, cam->dn_guide) : !P.d_gn);
+        if (spec)
+            session_specular_guides(cam, c, cam->dn_guide, io.stream);
+        else
+            session_guides(cam, c, io.stream);
+        const float4 *gn = spec ? P.d_sgn : P.d_gn, *gp = spec ? P.d_sgp : P.d_gp;
         if (o.var) prog_variance_pass(c, io.stream);
-        dn_filter(b, P.d_gn, P.d_gp, P.d_rad, C.width, io.r.x, io.r.y, io.r.width, io.r.height, o, radiance != nullptr,
+        dn_filter(b, gn, gp, P.d_rad, C.width, io.r.x, io.r.y, io.r.width, io.r.height, o, radiance != nullptr,
                   rgb != nullptr, variance_out != nullptr, io.stream, ev + 1);
         dn_outputs(b, io, o.var, radiance, variance_out, rgb);
     });
+}
+
+// The guide render: the pass `go` selects (null: first hit) over the region, unpacked into the
+// caller's arrays. The chain words go through the colour plane c0, which a guide render leaves free.
+static void guides_call(rt_camera* cam, const char* who, const rt_region* region, const rt_guide_options* go,
+                        float* normal, float* position, float* distance, int32_t* object, int32_t* chain) {
+    const RtCamera& C = cam->build.cam;
+    const RegionIo io{C.width, dn_region(region, C.width, C.height, who), nullptr};
+    DevCtx& c = cam->current();
+    c.ensure_device();
+    DnBufs& b = c.dn;
+    b.ensure((size_t)io.n());
+    const DenoiseGuides g{b.gn, b.gp};
+    int32_t* d_chain = chain ? reinterpret_cast<int32_t*>(b.c0.p) : nullptr;
+    c.launch_guide_pass(io.r, cam->traversal, g, io.stream, go, d_chain);
+    hip_check(launch_guides_unpack(g, io.n(), b.nrm(), b.pos(), b.dist(), b.obj, io.stream), "guides_unpack_kernel");
+    io.down(normal, b.nrm(), 3 * sizeof(float));
+    io.down(position, b.pos(), 3 * sizeof(float));
+    io.down(distance, b.dist(), sizeof(float));
+    io.down(object, b.obj, sizeof(int32_t));
+    io.down(chain, d_chain, sizeof(int32_t));
+    hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
 }
 
 extern "C" {
@@ -121,21 +150,30 @@ extern "C" {
 int rt_camera_render_guides(rt_camera* cam, const rt_region* region, float* normal, float* position, float* distance,
                             int32_t* object) {
     return camera_call(cam, [&] {
-        const RtCamera& C = cam->build.cam;
-        const RegionIo io{C.width, dn_region(region, C.width, C.height, "rt_camera_render_guides"), nullptr};
-        DevCtx& c = cam->current();
-        c.ensure_device();
-        DnBufs& b = c.dn;
-        b.ensure((size_t)io.n());
-        const DenoiseGuides g{b.gn, b.gp};
-        c.launch_guide_pass(io.r, cam->traversal, g, io.stream);
-        hip_check(launch_guides_unpack(g, io.n(), b.nrm(), b.pos(), b.dist(), b.obj, io.stream), "guides_unpack_kernel");
-        io.down(normal, b.nrm(), 3 * sizeof(float));
-        io.down(position, b.pos(), 3 * sizeof(float));
-        io.down(distance, b.dist(), sizeof(float));
-        io.down(object, b.obj, sizeof(int32_t));
-        hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
+        guides_call(cam, "rt_camera_render_guides", region, nullptr, normal, position, distance, object, nullptr);
     });
+}
+
+void rt_guide_options_default(rt_guide_options* options) {
+    if (options) *options = rt_guide_options{RT_GUIDES_FIRST_HIT, 8, 0.0f};
+}
+
+int rt_camera_render_guides_ex(rt_camera* cam, const rt_region* region, const rt_guide_options* options, float* normal,
+                               float* position, float* distance, int32_t* object, int32_t* chain) {
+    return camera_call(cam, [&] {
+        const char* who = "rt_camera_render_guides_ex";
+        const rt_guide_options go = guide_options(options, who);
+        guides_call(cam, who, region, &go, normal, position, distance, object, chain);
+    });
+}
+
+int rt_camera_set_denoise_guides(rt_camera* cam, const rt_guide_options* options) {
+    return camera_call(cam, [&] { cam->dn_guide = guide_options(options, "rt_camera_set_denoise_guides"); });
+}
+
+int rt_camera_get_denoise_guides(rt_camera* cam, rt_guide_options* options) {
+    if (!options) return set_error(RT_ERR_INVALID, "null argument");
+    return camera_call(cam, [&] { *options = cam->dn_guide; });
 }
 
 int rt_denoise(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,

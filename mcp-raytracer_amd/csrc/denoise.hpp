@@ -35,6 +35,19 @@ struct DenoiseGuides {
 hipError_t launch_guides(const DevScene& S, int trav, const RtRegion& reg, const int32_t* prim_object,
                          const DenoiseGuides& g, int lds_max, hipStream_t stream);
 
+// The guides at the first non-specular surface along the pixel's specular chain (guide_walk.hip;
+// tests/guide_walk_ref.py is the definition, include/rt_amd.h restates it): segment 0 is
+// launch_guides' ray, and a fuzz <= max_fuzz metal, glass, or what a mixed / layered material
+// resolves to continues the walk by one deterministic direction, up to max_bounces times. Same
+// outputs and layout, the distance summed over the segments; chain (region-packed int32, or
+// null) receives segments continued | end code << 8 (0 miss, 1 terminal surface, 2 the chain
+// left the scene: the last specular surface is the guide, 3 max_bounces reached).
+hipError_t launch_guide_walk(const DevScene& S, int trav, const RtRegion& reg, const int32_t* prim_object,
+                             const DenoiseGuides& g, int32_t* chain, int max_bounces, float max_fuzz, int lds_max,
+                             hipStream_t stream);
+// The chain word of first-hit guides: hit ? 1 << 8 : 0, from gp's object bits.
+hipError_t launch_guides_chain(const DenoiseGuides& g, int n, int32_t* chain, hipStream_t stream);
+
 // gn / gp -> the caller-facing arrays (region-packed: normal, position float[3], distance float,
 // object int32; any may be null), and back (explicit guides, rt_denoise).
 hipError_t launch_guides_unpack(const DenoiseGuides& g, int n, float* normal, float* position, float* distance,

@@ -524,7 +524,8 @@ hipEvent_t* DevCtx::dn_events(int levels) {
     return dn_ev.data();
 }
 
-void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream) {
+void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream,
+                               const rt_guide_options* go, int32_t* chain) {
     const RtCamera& C = build.cam;
     if (!d_prim_object) {
         std::vector<int32_t> po(std::max<size_t>(C.n_prims, 1), -1);
@@ -536,9 +537,15 @@ void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides
     const int tr = effective_traversal(trav);
     if (stack_lds_bytes(C.stack_depth, tr, C.n_prims) > (size_t)lds_max)
         throw std::runtime_error("traversal stack exceeds the workgroup LDS (BVH too deep)");
-    hip_check(launch_guides(dev_scene(), tr, RtRegion{r.x, r.y, r.width, r.height, 0, 1}, d_prim_object, g, lds_max,
-                            stream),
-              "guide_kernel launch");
+    const RtRegion reg{r.x, r.y, r.width, r.height, 0, 1};
+    if (go && go->mode == RT_GUIDES_SPECULAR) {
+        hip_check(launch_guide_walk(dev_scene(), tr, reg, d_prim_object, g, chain, go->max_bounces, go->max_fuzz, lds_max,
+                                    stream),
+                  "guide_walk_kernel launch");
+        return;
+    }
+    hip_check(launch_guides(dev_scene(), tr, reg, d_prim_object, g, lds_max, stream), "guide_kernel launch");
+    hip_check(launch_guides_chain(g, r.width * r.height, chain, stream), "guides_chain_kernel");
 }
 
 hipEvent_t* DevCtx::rp_events() {

@@ -67,6 +67,8 @@ struct CamHost {
     int32_t precision = PREC_REF;
     int32_t traversal = TRAV_AUTO;
     double mix_total = 0.5, light_w = 0.0;
+    // the guides the camera's filter calls compute (rt_camera_set_denoise_guides)
+    rt_guide_options dn_guide{RT_GUIDES_FIRST_HIT, 8, 0.0f};
 
     // The strategy a launch actually uses: BRUTE/FAST are exact only where every
     // primitive lies inside its reference box (scene.cpp prims_inside_boxes).
@@ -212,6 +214,11 @@ struct DevCtx {
         DevBuf<int32_t> d_pxs, d_pxb;
         DevBuf<float4> d_gn;  // the region's guides (denoise.hpp), computed by the first
         DevBuf<float4> d_gp;  // rt_camera_progressive_denoise of the session
+        // the region's guides through the specular chain (guide_walk.hip), of the options sg_key:
+        // a pair of their own - reprojection, accumulation and focus read d_gn / d_gp
+        DevBuf<float4> d_sgn, d_sgp;
+        rt_guide_options sg_key{};
+        bool sg_valid = false;
         // Focused steps (focus.hpp), allocated by the first one: the selected slots, the score
         // keys of the active entries, the selection's words (counts, T, digit states and
         // histograms) and their host copy, an uploaded score map, the full-frame selected mask,
@@ -255,7 +262,10 @@ struct DevCtx {
     hipEvent_t* dn_events(int levels);
 
     // The guide pass over `r` (clamped) into g, through the strategy `trav` resolves to; queued.
-    void launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream);
+    // go (null: first hit) selects the walk through the specular chain; chain (region-packed, or
+    // null) receives either pass's chain word.
+    void launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream,
+                           const rt_guide_options* go = nullptr, int32_t* chain = nullptr);
 
     // ---- Reprojection (reproject.hpp) -----------------------------------------------------------
     // As the NEW view's context: the reusable table and the events of the last call. As the

@@ -99,6 +99,35 @@ void session_guides(rt_camera* cam, DevCtx& c, hipStream_t stream) {
     }
 }
 
+rt_guide_options guide_options(const rt_guide_options* o, const std::string& who) {
+    rt_guide_options g;
+    rt_guide_options_default(&g);
+    if (o) g = *o;
+    if (g.mode != RT_GUIDES_FIRST_HIT && g.mode != RT_GUIDES_SPECULAR)
+        throw std::invalid_argument(who + ": mode must be RT_GUIDES_FIRST_HIT or RT_GUIDES_SPECULAR");
+    if (g.max_bounces < 1 || g.max_bounces > 64) throw std::invalid_argument(who + ": max_bounces must be 1..64");
+    if (!(g.max_fuzz >= 0.0f) || !std::isfinite(g.max_fuzz))
+        throw std::invalid_argument(who + ": max_fuzz must not be negative and be finite");
+    return g;
+}
+
+bool session_specular_cached(const DevCtx& c, const rt_guide_options& go) {
+    const DevCtx::ProgSession& P = c.prog;
+    return P.sg_valid && P.sg_key.max_bounces == go.max_bounces && P.sg_key.max_fuzz == go.max_fuzz;
+}
+
+void session_specular_guides(rt_camera* cam, DevCtx& c, const rt_guide_options& go, hipStream_t stream) {
+    DevCtx::ProgSession& P = c.prog;
+    if (session_specular_cached(c, go)) return;
+    const size_t n = (size_t)P.region.width * P.region.height;
+    P.sg_valid = false;
+    P.d_sgn.ensure(n, "hipMalloc(session guides)");
+    P.d_sgp.ensure(n, "hipMalloc(session guides)");
+    c.launch_guide_pass(P.region, cam->traversal, DenoiseGuides{P.d_sgn, P.d_sgp}, stream, &go);
+    P.sg_key = go;
+    P.sg_valid = true;
+}
+
 void prog_variance_pass(DevCtx& c, hipStream_t stream) {
     DevCtx::ProgSession& P = c.prog;
     c.dn.var.ensure((size_t)P.region.width * P.region.height, "hipMalloc(denoise variance)");

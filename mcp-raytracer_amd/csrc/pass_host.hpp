@@ -61,6 +61,13 @@ void session_on_device(const DevCtx& c, const std::string& who);
 DevCtx& session_with(rt_camera* cam, const std::string& who, int min_samples);
 // The session's guides: computed once (queued), freed with the session.
 void session_guides(rt_camera* cam, DevCtx& c, hipStream_t stream);
+// rt_guide_options as the caller gave them (NULL: rt_guide_options_default), checked: an unknown
+// mode, max_bounces outside 1..64 and a negative or non-finite max_fuzz are argument errors.
+rt_guide_options guide_options(const rt_guide_options* o, const std::string& who);
+// The session's guides through the specular chain for the options `go`: true when they are the
+// kept ones, else recomputed (queued). Freed with the session.
+bool session_specular_cached(const DevCtx& c, const rt_guide_options& go);
+void session_specular_guides(rt_camera* cam, DevCtx& c, const rt_guide_options& go, hipStream_t stream);
 // The session's state -> c.dn.var (region-packed); queued.
 void prog_variance_pass(DevCtx& c, hipStream_t stream);
 // Queues the copy of the session region's rows of a full-frame device array (`elem` bytes per

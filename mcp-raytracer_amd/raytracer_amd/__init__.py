@@ -14,7 +14,8 @@ ProgressiveRender (resumable sample steps with a preview and checkpoints), and f
 guide buffers with a guided edge-avoiding a-trous filter for low-sample frames:
 Camera.render_guides / Camera.denoise / denoise / ProgressiveRender.denoised; a session's
 per-pixel variance map (ProgressiveRender.variance, progressive_blob_variance) guides that filter
-when `variance=` is passed to any of them. A previous view's frame is reprojected into a moved
+when `variance=` is passed to any of them, and `guides="specular"` /
+render_guides(through_specular=True) take the guides behind mirrors and glass. A previous view's frame is reprojected into a moved
 camera's view by Camera.reproject / reproject / ProgressiveRender.reprojected (Camera.view,
 Camera.reusable_objects), so the first frames of a new view start from the last view's history. A History follows a camera
 along a path on the device: ProgressiveRender.accumulated blends each view's frame onto it by

@@ -51,6 +51,9 @@ _UNITS = [
     # (no contraction; plain / and sqrtf are IEEE under hipcc's defaults) - the output equals
     # tests/denoise_ref.py and tests/denoise_var_ref.py in every bit
     ("denoise.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the guides through the specular chain: the same rule - the output equals
+    # tests/guide_walk_ref.py in every bit
+    ("guide_walk.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the reprojection gather: as the filter, every fp32 operation rounds once - the output equals
     # tests/reproject_ref.py in every bit
     ("reproject.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),

@@ -101,6 +101,13 @@ class RtDenoiseVarOptions(C.Structure):
 DENOISE_MAX_LEVELS = 8
 
 
+GUIDES_FIRST_HIT, GUIDES_SPECULAR = 0, 1  # RT_GUIDES_*
+
+
+class RtGuideOptions(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_bounces", C.c_int32), ("max_fuzz", C.c_float)]
+
+
 class RtView(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("pixel00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
                 ("width", C.c_int32), ("height", C.c_int32)]
@@ -237,6 +244,11 @@ _SIGS = {
     "rt_camera_progressive_end": (C.c_int, [C.c_void_p]),
     "rt_camera_render_guides": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "rt_guide_options_default": (None, [C.POINTER(RtGuideOptions)]),
+    "rt_camera_render_guides_ex": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.POINTER(RtGuideOptions), C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_set_denoise_guides": (C.c_int, [C.c_void_p, C.POINTER(RtGuideOptions)]),
+    "rt_camera_get_denoise_guides": (C.c_int, [C.c_void_p, C.POINTER(RtGuideOptions)]),
     "rt_denoise": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.POINTER(RtDenoiseOptions), C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_camera_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.POINTER(RtDenoiseOptions), C.c_void_p,

@@ -100,6 +100,18 @@ def _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma
     return True, _lib.RtDenoiseVarOptions(int(levels), float(sigma_variance), float(sigma_plane))
 
 
+def _guide_options(guides) -> _lib.RtGuideOptions:
+    """rt_guide_options of a `guides=` keyword: "first_hit", "specular" (max_bounces 8, max_fuzz 0)
+    or a dict of max_bounces / max_fuzz for the specular walk (the library validates the values)."""
+    if isinstance(guides, str) and guides == "first_hit":
+        return _lib.RtGuideOptions(_lib.GUIDES_FIRST_HIT, 8, 0.0)
+    if isinstance(guides, str) and guides == "specular":
+        guides = {}
+    if not isinstance(guides, dict) or set(guides) - {"max_bounces", "max_fuzz"}:
+        raise ValueError('guides must be "first_hit", "specular" or a dict of max_bounces / max_fuzz')
+    return _lib.RtGuideOptions(_lib.GUIDES_SPECULAR, int(guides.get("max_bounces", 8)), float(guides.get("max_fuzz", 0.0)))
+
+
 def _var_out(variance_out, shape):
     """Pointer of the optional caller-owned (H, W) float32 array the filtered variance goes to."""
     import numpy as np
@@ -135,7 +147,7 @@ def _denoise_out(src, out):
 
 
 def denoise(radiance, normal, position, distance, object, region=None, *, levels=4, sigma_color=None,
-            sigma_plane=0.01, rgb=None, out=None, variance=None, sigma_variance=2.0, variance_out=None):
+            sigma_plane=0.01, rgb=None, out=None, variance=None, sigma_variance=2.0, variance_out=None, chain=None):
     """rt_denoise: the guided edge-avoiding a-trous filter of a frame with explicit guides (as
     Camera.render_guides returns them), no camera. radiance / normal / position: float32
     (H, W, 3); distance float32, object int32: (H, W). Returns the filtered radiance (H, W, 3) -
@@ -147,7 +159,8 @@ def denoise(radiance, normal, position, distance, object, region=None, *, levels
     ProgressiveRender.variance returns it) selects the variance-guided filter
     (rt_denoise_variance, tests/denoise_var_ref.py) with `sigma_variance` in place of
     sigma_color; `variance_out` (optional float32 (H, W)) then receives the region's filtered
-    variance. Passing sigma_color together with variance raises ValueError."""
+    variance. Passing sigma_color together with variance raises ValueError. `chain` is accepted
+    and ignored, so denoise(radiance, **cam.render_guides(through_specular=True)) works."""
     import numpy as np
     rad = np.asarray(radiance)
     if rad.ndim != 3 or rad.shape[2] != 3:
@@ -625,32 +638,54 @@ class Camera:
         return ProgressiveRender(self)
 
     # -- guides and the denoised preview ------------------------------------------
-    def render_guides(self, region=None) -> dict:
+    def render_guides(self, region=None, *, through_specular=False, max_bounces=8, max_fuzz=0.0) -> dict:
         """First-hit guide buffers (rt_camera_render_guides): one deterministic pinhole primary
         ray per pixel of `region` (default: the whole image). Returns full-frame arrays
         {"normal": float32 (H, W, 3), "position": float32 (H, W, 3), "distance": float32 (H, W),
         "object": int32 (H, W): index in SceneData.objects, -1 on a miss}; pixels outside the
-        region hold zeros (object -1)."""
+        region hold zeros (object -1).
+
+        `through_specular=True` (rt_camera_render_guides_ex, RT_GUIDES_SPECULAR) follows mirrors
+        (metals of fuzz <= max_fuzz) and glass for up to `max_bounces` continuations to the first
+        surface that is not specular: the same four arrays, the distance summed along the chain,
+        and "chain": int32 (H, W) = continuations | end code << 8 (0 miss, 1 terminal surface,
+        2 the chain left the scene, 3 max_bounces reached), zero outside the region. Equals
+        tests/guide_walk_ref.py in every bit."""
         import numpy as np
         H, W = self.image_height, self.image_width
         g = {"normal": np.zeros((H, W, 3), np.float32), "position": np.zeros((H, W, 3), np.float32),
              "distance": np.zeros((H, W), np.float32), "object": np.full((H, W), -1, np.int32)}
         reg = None if region is None else _region(region)
-        _lib.check(self._lib.rt_camera_render_guides(self._h, C.byref(reg) if reg is not None else None,
-                                                     g["normal"].ctypes.data, g["position"].ctypes.data,
-                                                     g["distance"].ctypes.data, g["object"].ctypes.data))
+        rptr = C.byref(reg) if reg is not None else None
+        if through_specular:
+            g["chain"] = np.zeros((H, W), np.int32)
+            opts = _lib.RtGuideOptions(_lib.GUIDES_SPECULAR, int(max_bounces), float(max_fuzz))
+            _lib.check(self._lib.rt_camera_render_guides_ex(self._h, rptr, C.byref(opts), g["normal"].ctypes.data,
+                                                            g["position"].ctypes.data, g["distance"].ctypes.data,
+                                                            g["object"].ctypes.data, g["chain"].ctypes.data))
+        else:
+            _lib.check(self._lib.rt_camera_render_guides(self._h, rptr, g["normal"].ctypes.data,
+                                                         g["position"].ctypes.data, g["distance"].ctypes.data,
+                                                         g["object"].ctypes.data))
         return g
 
+    def _set_denoise_guides(self, guides) -> None:
+        opts = _guide_options(guides)
+        _lib.check(self._lib.rt_camera_set_denoise_guides(self._h, C.byref(opts)))
+
     def denoise(self, radiance, region=None, *, levels=4, sigma_color=None, sigma_plane=0.01, rgb=None, out=None,
-                variance=None, sigma_variance=2.0, variance_out=None):
+                variance=None, sigma_variance=2.0, variance_out=None, guides="first_hit"):
         """rt_camera_denoise: the a-trous filter of a frame of this camera (float32 (H, W, 3), as
         render_region's `radiance`), its guides computed on the device. Returns the filtered
         radiance (H, W, 3) - a new array, or `out` (which may be `radiance` itself); `rgb`
         (optional u8 W*H*3) receives the region's u8. Equals denoise(radiance,
         **render_guides(region), region=region, ...). `variance` (float32 (H, W)), `sigma_variance`
         and `variance_out` select the variance-guided filter (rt_camera_denoise_variance) as in
-        denoise()."""
+        denoise(). `guides` selects the guides the call computes (rt_camera_set_denoise_guides):
+        "first_hit", "specular" - those of render_guides(through_specular=True) - or a dict of
+        max_bounces / max_fuzz for the latter."""
         H, W = self.image_height, self.image_width
+        self._set_denoise_guides(guides)
         rad = _f32_frame(radiance, (H, W, 3), "radiance")
         res = _denoise_out(rad, out)
         uptr, _k = _host_ptr(rgb, self.byte_length, "rgb")
@@ -879,7 +914,7 @@ class ProgressiveRender:
         return out if out.shape == shape else out.reshape(shape)
 
     def denoised(self, buffer=None, radiance=None, *, levels=4, sigma_color=None, sigma_plane=0.01, variance=False,
-                 sigma_variance=2.0, variance_out=None):
+                 sigma_variance=2.0, variance_out=None, guides="first_hit"):
         """The session's frame as it stands after the last step, through the a-trous filter
         (rt_camera_progressive_denoise): the frame never leaves the device, the region's guides
         are computed on first use and kept, and the session itself is not touched. `buffer` (u8
@@ -889,11 +924,14 @@ class ProgressiveRender:
         variance-guided filter on the variance of the session's own state
         (rt_camera_progressive_denoise_variance; needs samples_done >= 2) with `sigma_variance`
         in place of sigma_color; `variance_out` (optional float32 (H, W)) receives the region's
-        filtered variance."""
+        filtered variance. `guides` as in Camera.denoise: the session keeps its specular guides
+        beside the first-hit ones (which reprojected / accumulate / focus always use) and
+        recomputes them when max_bounces or max_fuzz change."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
         import numpy as np
         cam = self._cam
+        cam._set_denoise_guides(guides)
         if radiance is None:
             radiance = np.zeros((cam.image_height, cam.image_width, 3), np.float32)
         ptr, _k0 = _host_ptr(buffer, cam.byte_length, "buffer")
