@@ -606,8 +606,9 @@ int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_
  * guide_ms covers whichever pass ran. RT_ERR_INVALID, decided before any device call: an unknown
  * mode, max_bounces outside 1..64, a negative or non-finite max_fuzz.
  * Limits: one deterministic branch per interface (no Schlick split), fuzzy metals above max_fuzz
- * are terminal, a defocused camera's blur is not in the guides, and reprojection and the view
- * history still stop at specular surfaces. Not in the N-API addon or the multi-GPU render. */
+ * are terminal, a defocused camera's blur is not in the guides, and rt_reproject and the view
+ * history still stop at specular surfaces (rt_reproject_specular and its camera calls, below,
+ * follow the chains on request). Not in the N-API addon or the multi-GPU render. */
 enum { RT_GUIDES_FIRST_HIT = 0, RT_GUIDES_SPECULAR = 1 };
 typedef struct { int32_t mode; int32_t max_bounces; float max_fuzz; } rt_guide_options;
 void rt_guide_options_default(rt_guide_options* options);
@@ -645,7 +646,8 @@ int rt_camera_get_denoise_guides(rt_camera* cam, rt_guide_options* options);
  * every bit.
  *
  * Limits. The guides are pinhole first hits: view-dependent surfaces (metal, glass, mixed,
- * layered: reusable = 0) and misses get no history, and a defocus camera's blur is not in them.
+ * layered: reusable = 0) and misses get no history (what a mirror or glass shows can get one
+ * through rt_reproject_specular, below), and a defocus camera's blur is not in them.
  * The lighting must not have changed between the views. The history is weighted by the constant
  * history_samples, whatever the previous frame's own sample counts.
  *
@@ -689,6 +691,82 @@ int rt_camera_progressive_reproject(rt_camera* cam, rt_camera* prev_cam, const r
  * HIP events: the guide passes (both views'; a session reuses its own), the gather kernel, and
  * the whole span guide passes .. unpacked outputs (host copies excluded). Waits for the events. */
 int rt_camera_reproject_times(rt_camera* cam, float* guide_ms, float* reproject_ms, float* total_ms);
+
+/* ---- Reprojection through mirrors and glass (specular chains) ----------------------------------
+ * Opt-in like the blocks above: no other call changes. The radiance a pixel receives along a
+ * chain of perfect mirrors that ends on a Lambertian or emissive surface does not depend on the
+ * viewer, and through a planar mirror the previous view sees that surface point at the same
+ * virtual location: the point at the chain's summed path length along the primary ray.
+ * tests/specular_reproject_ref.py is the normative definition; in words, with the rules of the
+ * reprojection block (fp32, no fused multiply-add, its dot, projection, taps and blend):
+ *
+ * Per pixel of the new region: the first-hit guides n1, P1, D1, o1; the guides through the chain
+ * n, P, Ds, o and the chain word ch of ONE rt_guide_options (mode RT_GUIDES_SPECULAR), k = ch & 0xff,
+ * e = (ch >> 8) & 0xff; the new view's centre cn; the previous view V with the constants above and
+ * pix2 = du.du / a.a; the previous view's first-hit planes, chain planes and chain words, walked
+ * with the same options; two byte tables per object, reusable (above) and through.
+ *   k == 0  the reprojection block verbatim on n1, P1, D1, o1 against the previous first-hit
+ *           planes; kind = 1 where weight > 0.
+ *   k >= 1  no history unless e == 1, 0 <= o < n_objects and reusable[o], 0 <= o1 < n_objects and
+ *           through[o1], P and P1 finite, Ds finite, D1 finite and > 0. Then r = Ds / D1,
+ *           X = cn + (P1 - cn) r (subtract, multiply, add), and X is projected in place of P with
+ *           the same validity tests, taps and weights. A tap counts iff it lies inside the previous
+ *           image and prev_region, its chain word equals ch, its first-hit object equals o1, its
+ *           chain object equals o, its radiance is finite, n.n' >= normal_min,
+ *           |n.(P' - P)| <= sigma_plane Ds and q.q <= (pp2 Ds) Ds with q = P' - P,
+ *           pp2 = (point_pixels point_pixels) pix2 - n', P' the tap's chain guides. ws, acc,
+ *           min_weight, history and the blend as above; kind = 2 where weight > 0.
+ * The point check asks that the previous pixel showed the same surface point, not only the same
+ * plane, within point_pixels footprints of a previous pixel at the chain's length.
+ * through[o] = 1 iff object o's resolved top-level material class is in a mask: 1 a metal of fuzz
+ * <= max_fuzz, 2 glass, 4 mixed, 8 layered (default 15: everything the walk follows). Only the
+ * chain's first object is checked; longer chains are tied down by the equal chain word, the equal
+ * first and last objects and the point check.
+ *
+ * Limits. A curved mirror's image does not lie at the summed length, so it gets little or no
+ * history; grazing reflections are under-covered by the isotropic point check; through glass the
+ * Schlick split varies with the angle, so the history is an approximation; chains that leave the
+ * scene (end code 2) or reach max_bounces get no history; the lighting must be unchanged.
+ *
+ * Buffers and errors as the reprojection block; kind_out: width*height uint8 (0 none, 1 first hit,
+ * 2 chain). Also RT_ERR_INVALID before any device call: guide options rt_camera_render_guides_ex
+ * would refuse, mode RT_GUIDES_FIRST_HIT, a negative or non-finite point_pixels, a through mask
+ * outside 0..15. rt_camera_release_device frees every device buffer of the camera calls, and
+ * rt_camera_reproject_times covers them (guide_ms: all four guide passes; a session reuses its own). */
+typedef struct { rt_reproject_options base; float point_pixels; int32_t through; } rt_specular_reproject_options;   /* NULL or a zero field = default (base's, 4, 15) */
+/* {{0.9, 0.01, 0.25, 32}, 4, 15}. Host only. */
+void rt_specular_reproject_options_default(rt_specular_reproject_options* options);
+/* through[o] for the mask and max_fuzz (from the build's material table, ids followed); out holds
+ * rt_camera_info.n_objects bytes (capacity below that: RT_ERR_INVALID). Host only. */
+int rt_camera_through_objects(const rt_camera* cam, int32_t mask, float max_fuzz, uint8_t* out, int32_t capacity);
+/* explicit buffers, no camera (the calling thread's current device); view: the new view */
+int rt_reproject_specular(int32_t width, int32_t height, const rt_region* region, const float* normal,
+                          const float* position, const float* distance, const int32_t* object,
+                          const float* chain_normal, const float* chain_position, const float* chain_distance,
+                          const int32_t* chain_object, const int32_t* chain, const rt_view* view,
+                          const rt_view* prev_view, const rt_region* prev_region, const float* prev_radiance,
+                          const float* prev_normal, const float* prev_position, const float* prev_distance,
+                          const int32_t* prev_object, const float* prev_chain_normal, const float* prev_chain_position,
+                          const float* prev_chain_distance, const int32_t* prev_chain_object, const int32_t* prev_chain,
+                          const uint8_t* reusable, const uint8_t* through, int32_t n_objects,
+                          const rt_specular_reproject_options* options, const float* radiance, const int32_t* px_samples,
+                          int32_t samples, float* history_out, float* weight_out, float* radiance_out, uint8_t* rgb_out,
+                          uint8_t* kind_out);
+/* Both cameras' two guide passes run on the calling thread's device and never reach the host;
+ * guide_options NULL = {RT_GUIDES_SPECULAR, 8, 0}; the through table is cam's for options->through
+ * and guide_options->max_fuzz. The cameras must hold the same scene, as rt_camera_reproject. */
+int rt_camera_reproject_specular(rt_camera* cam, const rt_region* region, rt_camera* prev_cam,
+                                 const rt_region* prev_region, const rt_guide_options* guide_options,
+                                 const rt_specular_reproject_options* options, const float* prev_radiance,
+                                 const float* radiance, const int32_t* px_samples, int32_t samples, float* history_out,
+                                 float* weight_out, float* radiance_out, uint8_t* rgb_out, uint8_t* kind_out);
+/* rt_camera_progressive_reproject through the chains: the session's kept first-hit and chain
+ * guides serve (the chain plane is kept beside the latter); its state, frame, stats and
+ * checkpoint bytes are not touched. */
+int rt_camera_progressive_reproject_specular(rt_camera* cam, rt_camera* prev_cam, const rt_region* prev_region,
+                                             const rt_guide_options* guide_options,
+                                             const rt_specular_reproject_options* options, const float* prev_radiance,
+                                             uint8_t* rgb, float* radiance, float* weight_out, uint8_t* kind_out);
 
 /* ---- Accumulation across views: per-pixel history length and variance -------------------------
  * A view history follows a camera along a path. Per pixel it keeps the accumulated radiance c',

@@ -8,37 +8,6 @@
 
 using namespace rt;
 
-// rt_reproject_options resolved: a zero field = the default.
-struct RpOpts : GatherOpts {
-    float nh;
-};
-static RpOpts rp_resolve(const rt_reproject_options* o, const std::string& who) {
-    const rt_reproject_options z = o ? *o : rt_reproject_options{0.0f, 0.0f, 0.0f, 0.0f};
-    RpOpts r{gather_resolve(z.normal_min, z.sigma_plane, z.min_weight, who), 0.0f};
-    r.nh = resolve_field(z.history_samples, 32.0f, who, "history_samples");
-    return r;
-}
-
-// The argument errors every reproject entry shares (host only).
-static void rp_check(const std::string& who, const float* prev_radiance, const float* radiance, int32_t samples,
-                     const float* radiance_out, const uint8_t* rgb_out) {
-    if (!prev_radiance) throw std::invalid_argument(who + ": prev_radiance is required");
-    if ((radiance_out || rgb_out) && !radiance)
-        throw std::invalid_argument(who + ": radiance_out and rgb_out need a fresh radiance to blend");
-    if (samples < 0) throw std::invalid_argument(who + ": samples must not be negative");
-}
-
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
-static void rp_same_scene(const rt_camera* a, const rt_camera* b) {
-    const SceneBuild &x = a->build, &y = b->build;
-    if (a != b && !(same_bytes(x.nodes, y.nodes) && same_bytes(x.prims, y.prims) && same_bytes(x.mats, y.mats) &&
-                    same_bytes(x.lights, y.lights) && same_bytes(x.prim_object, y.prim_object)))
-        throw std::invalid_argument("reproject: the cameras hold different scenes");
-}
-
 // The device side of a call once both views' guides and the previous radiance (pb.rad(),
 // region-packed) are there: the previous colour packed as the plain filter packs it, the gather,
 // then history -> nb.nrm(), weight -> nb.dist(), the blend -> nb.rad() / nb.u8. ev (or null):

@@ -80,6 +80,10 @@ void DevCtx::release() {
         if (e) (void)hipEventDestroy(e), e = nullptr;
     rp_ev.clear();
     rp_timed = false;
+    rs.free();
+    rs_prev.free();
+    d_through.reset();
+    through_mask = -1;
     d_acount.reset();
     if (h_acount) (void)hipHostFree(h_acount);
     h_acount = nullptr;

@@ -219,6 +219,9 @@ struct DevCtx {
         DevBuf<float4> d_sgn, d_sgp;
         rt_guide_options sg_key{};
         bool sg_valid = false;
+        // the chain plane of that walk, kept once a reprojection through the chains asked for it
+        DevBuf<int32_t> d_sch;
+        bool sch_valid = false;
         // Focused steps (focus.hpp), allocated by the first one: the selected slots, the score
         // keys of the active entries, the selection's words (counts, T, digit states and
         // histograms) and their host copy, an uploaded score map, the full-frame selected mask,
@@ -281,7 +284,28 @@ struct DevCtx {
     // The reusable table on the device (uploaded once: the scene never changes).
     const uint8_t* ensure_reusable();
 
-    int adapt_rounds = 0;                   // rounds of the last adaptive render
+    // ---- Reprojection through specular chains (reproject_spec.hpp) ------------------------------
+    // One view's guides through the chain and its chain plane, region-packed, beside the first-hit
+    // pair in dn / rp_prev: rs as the NEW view's context (with the call's kind plane), rs_prev as
+    // the PREVIOUS view's - a camera may be both views of one call.
+    struct RsBufs {
+        DevBuf<float4> sgn, sgp;
+        DevBuf<int32_t> chain;
+        DevBuf<uint8_t> kind;
+        void ensure(size_t n) {
+            sgn.ensure(n, "hipMalloc(chain guides)");
+            sgp.ensure(n, "hipMalloc(chain guides)");
+            chain.ensure(n, "hipMalloc(chain guides)");
+            kind.ensure(n, "hipMalloc(chain guides)");
+        }
+        void free() { *this = RsBufs{}; }
+    } rs, rs_prev;
+    // object index -> 1: a chain may start on it, for the mask and max_fuzz it was built from
+    DevBuf<uint8_t> d_through;
+    int32_t through_mask = -1;
+    float through_fuzz = 0.0f;
+
+    int adapt_rounds = 0;                  // rounds of the last adaptive render
     unsigned long long adapt_rendered = 0;  // samples its rounds rendered (>= the samples kept)
     // Adaptive rounds: per-slot running PixelStats, two active lists, the list counter.
     DevBuf<AdaptPix> d_astate;

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <vector>
 
 namespace rt {
 
@@ -18,6 +20,32 @@ GatherOpts gather_resolve(float normal_min, float sigma_plane, float min_weight,
     o.sigma_plane = resolve_field(sigma_plane, 0.01f, who, "sigma_plane");
     o.min_weight = resolve_field(min_weight, 0.25f, who, "min_weight");
     return o;
+}
+
+RpOpts rp_resolve(const rt_reproject_options* o, const std::string& who) {
+    const rt_reproject_options z = o ? *o : rt_reproject_options{0.0f, 0.0f, 0.0f, 0.0f};
+    RpOpts r{gather_resolve(z.normal_min, z.sigma_plane, z.min_weight, who), 0.0f};
+    r.nh = resolve_field(z.history_samples, 32.0f, who, "history_samples");
+    return r;
+}
+
+void rp_check(const std::string& who, const float* prev_radiance, const float* radiance, int32_t samples,
+              const float* radiance_out, const uint8_t* rgb_out) {
+    if (!prev_radiance) throw std::invalid_argument(who + ": prev_radiance is required");
+    if ((radiance_out || rgb_out) && !radiance)
+        throw std::invalid_argument(who + ": radiance_out and rgb_out need a fresh radiance to blend");
+    if (samples < 0) throw std::invalid_argument(who + ": samples must not be negative");
+}
+
+template <class T>
+static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
+    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
+void rp_same_scene(const rt_camera* a, const rt_camera* b) {
+    const SceneBuild &x = a->build, &y = b->build;
+    if (a != b && !(same_bytes(x.nodes, y.nodes) && same_bytes(x.prims, y.prims) && same_bytes(x.mats, y.mats) &&
+                    same_bytes(x.lights, y.lights) && same_bytes(x.prim_object, y.prim_object)))
+        throw std::invalid_argument("reproject: the cameras hold different scenes");
 }
 
 constexpr long kDenoiseMaxPixels = 1l << 28;
@@ -111,21 +139,25 @@ rt_guide_options guide_options(const rt_guide_options* o, const std::string& who
     return g;
 }
 
-bool session_specular_cached(const DevCtx& c, const rt_guide_options& go) {
+bool session_specular_cached(const DevCtx& c, const rt_guide_options& go, bool want_chain) {
     const DevCtx::ProgSession& P = c.prog;
-    return P.sg_valid && P.sg_key.max_bounces == go.max_bounces && P.sg_key.max_fuzz == go.max_fuzz;
+    return P.sg_valid && P.sg_key.max_bounces == go.max_bounces && P.sg_key.max_fuzz == go.max_fuzz &&
+           (!want_chain || P.sch_valid);
 }
 
-void session_specular_guides(rt_camera* cam, DevCtx& c, const rt_guide_options& go, hipStream_t stream) {
+void session_specular_guides(rt_camera* cam, DevCtx& c, const rt_guide_options& go, hipStream_t stream, bool want_chain) {
     DevCtx::ProgSession& P = c.prog;
-    if (session_specular_cached(c, go)) return;
+    if (session_specular_cached(c, go, want_chain)) return;
     const size_t n = (size_t)P.region.width * P.region.height;
-    P.sg_valid = false;
+    P.sg_valid = P.sch_valid = false;
     P.d_sgn.ensure(n, "hipMalloc(session guides)");
     P.d_sgp.ensure(n, "hipMalloc(session guides)");
-    c.launch_guide_pass(P.region, cam->traversal, DenoiseGuides{P.d_sgn, P.d_sgp}, stream, &go);
+    if (want_chain) P.d_sch.ensure(n, "hipMalloc(session guides)");
+    c.launch_guide_pass(P.region, cam->traversal, DenoiseGuides{P.d_sgn, P.d_sgp}, stream, &go,
+                        want_chain ? P.d_sch.p : nullptr);
     P.sg_key = go;
     P.sg_valid = true;
+    P.sch_valid = want_chain;
 }
 
 void prog_variance_pass(DevCtx& c, hipStream_t stream) {

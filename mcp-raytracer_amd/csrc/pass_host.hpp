@@ -27,6 +27,17 @@ struct GatherOpts {
 };
 GatherOpts gather_resolve(float normal_min, float sigma_plane, float min_weight, const std::string& who);
 
+// rt_reproject_options resolved: a zero field = the default.
+struct RpOpts : GatherOpts {
+    float nh;
+};
+RpOpts rp_resolve(const rt_reproject_options* o, const std::string& who);
+// The argument errors every reproject entry shares (host only).
+void rp_check(const std::string& who, const float* prev_radiance, const float* radiance, int32_t samples,
+              const float* radiance_out, const uint8_t* rgb_out);
+// "reproject: the cameras hold different scenes" unless both builds are equal in every byte.
+void rp_same_scene(const rt_camera* a, const rt_camera* b);
+
 // `region` (NULL: the whole image) clamped to a width x height image; empty: an argument error.
 rt_region dn_region(const rt_region* region, int32_t width, int32_t height, const std::string& who);
 
@@ -66,8 +77,11 @@ void session_guides(rt_camera* cam, DevCtx& c, hipStream_t stream);
 rt_guide_options guide_options(const rt_guide_options* o, const std::string& who);
 // The session's guides through the specular chain for the options `go`: true when they are the
 // kept ones, else recomputed (queued). Freed with the session.
-bool session_specular_cached(const DevCtx& c, const rt_guide_options& go);
-void session_specular_guides(rt_camera* cam, DevCtx& c, const rt_guide_options& go, hipStream_t stream);
+// want_chain: the walk's chain plane is kept beside them (P.d_sch); kept guides without it are
+// walked again.
+bool session_specular_cached(const DevCtx& c, const rt_guide_options& go, bool want_chain = false);
+void session_specular_guides(rt_camera* cam, DevCtx& c, const rt_guide_options& go, hipStream_t stream,
+                             bool want_chain = false);
 // The session's state -> c.dn.var (region-packed); queued.
 void prog_variance_pass(DevCtx& c, hipStream_t stream);
 // Queues the copy of the session region's rows of a full-frame device array (`elem` bytes per

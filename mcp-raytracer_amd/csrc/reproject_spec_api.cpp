@@ -1,0 +1,308 @@
+// C ABI of the reprojection through specular chains (reproject_spec.hpp): the through-table
+// query and the stand-alone, camera and session calls. Their timings are rt_camera_reproject_times'.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "pass_host.hpp"
+#include "reproject_spec.hpp"
+
+using namespace rt;
+
+// rt_specular_reproject_options resolved: a zero field = the default.
+struct RsOpts {
+    RpOpts base;
+    float point_pixels;
+    int32_t through;
+};
+static RsOpts rs_resolve(const rt_specular_reproject_options* o, const std::string& who) {
+    rt_specular_reproject_options z{};
+    if (o) z = *o;
+    RsOpts r{rp_resolve(&z.base, who), 0.0f, 0};
+    r.point_pixels = resolve_field(z.point_pixels, 4.0f, who, "point_pixels");
+    if (z.through < 0 || z.through > 15) throw std::invalid_argument(who + ": through must be a mask in 0..15 (0: the default, 15)");
+    r.through = z.through ? z.through : 15;
+    return r;
+}
+
+// The guide options of a call: NULL = the specular walk's defaults; first-hit guides have no chains.
+static rt_guide_options rs_guide_options(const rt_guide_options* go, const std::string& who) {
+    const rt_guide_options dflt{RT_GUIDES_SPECULAR, 8, 0.0f};
+    const rt_guide_options g = guide_options(go ? go : &dflt, who);
+    if (g.mode != RT_GUIDES_SPECULAR) throw std::invalid_argument(who + ": guide_options must have mode RT_GUIDES_SPECULAR");
+    return g;
+}
+
+// through[o] = 1 iff SceneData.objects[o]'s material (resolved to a table index by the build) is
+// in `mask`: 1 a metal of fuzz <= max_fuzz (the walk's own comparison), 2 glass, 4 mixed, 8 layered.
+static std::vector<uint8_t> through_objects(const CamHost& h, int32_t mask, float max_fuzz) {
+    const SceneBuild& b = h.build;
+    std::vector<uint8_t> t((size_t)std::max(b.cam.n_prims, 0), 0);
+    for (size_t s = 0; s < b.prims.size() && s < b.prim_object.size(); ++s) {
+        const int32_t o = b.prim_object[s], m = b.prims[s].mat;
+        if (o < 0 || (size_t)o >= t.size() || m < 0 || (size_t)m >= b.mats.size()) continue;
+        const auto& mat = b.mats[m];
+        bool ok = false;
+        switch (mat.type) {
+            case MAT_METAL: ok = (mask & 1) && !(mat.p0 > (double)max_fuzz); break;
+            case MAT_GLASS: ok = (mask & 2) != 0; break;
+            case MAT_MIXED: ok = (mask & 4) != 0; break;
+            case MAT_LAYERED: ok = (mask & 8) != 0; break;
+            default: break;
+        }
+        t[o] = ok;
+    }
+    return t;
+}
+static void through_check(const std::string& who, int32_t mask, float max_fuzz) {
+    if (mask < 0 || mask > 15) throw std::invalid_argument(who + ": mask must be in 0..15");
+    if (!(max_fuzz >= 0.0f) || !std::isfinite(max_fuzz))
+        throw std::invalid_argument(who + ": max_fuzz must not be negative and be finite");
+}
+// The table on the device, rebuilt when the mask or max_fuzz change.
+static const uint8_t* ensure_through(DevCtx& c, int32_t mask, float max_fuzz) {
+    if (!c.d_through || c.through_mask != mask || c.through_fuzz != max_fuzz) {
+        std::vector<uint8_t> t = through_objects(c.host, mask, max_fuzz);
+        t.resize(std::max<size_t>(t.size(), 1), 0);
+        c.d_through.ensure(t.size(), "hipMalloc(through objects)");
+        hip_check(hipMemcpy(c.d_through, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        c.through_mask = mask;
+        c.through_fuzz = max_fuzz;
+    }
+    return c.d_through;
+}
+
+// (pp * pp) * (du.du / a.a): each product, sum and the division rounded once (this unit is
+// compiled without contraction).
+static float rs_pp2(const RpView& v, float pp) {
+    auto dot = [](const float* a, const float* b) {
+        const float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
+        const float xy = x + y;
+        return xy + z;
+    };
+    const float pix2 = dot(v.du, v.du) / dot(v.a, v.a);
+    const float p2 = pp * pp;
+    return p2 * pix2;
+}
+
+// The device side of a call once both views' guide planes and the previous radiance (pb.rad(),
+// region-packed) are there: the previous colour packed, the gather, then history -> nb.nrm(),
+// weight -> nb.dist(), the blend -> nb.rad() / nb.u8, kind -> d_kind. ev (or null): events 2..4 as
+// rt_camera_reproject's. Queued.
+static void rs_run(DnBufs& nb, DnBufs& pb, const RsGuides& ng, const RsGuides& pg, uint8_t* d_kind, const RpView& view,
+                   const float* cn, const rt_region& r, const rt_region& pr, const uint8_t* d_reusable,
+                   const uint8_t* d_through, int n_objects, const RsOpts& o, const RpNew& nw, bool want_hist, bool want_rad,
+                   bool want_u8, bool want_kind, hipStream_t stream, hipEvent_t* ev) {
+    auto mark = [&](int k) {
+        if (ev) hip_check(hipEventRecord(ev[k], stream), "hipEventRecord");
+    };
+    hip_check(launch_denoise_pack(pb.rad(), pr.width, 0, 0, pr.width, pr.height, pg.gn, 1.0f, nullptr, pb.c0, pb.fn, stream),
+              "denoise_pack_kernel");
+    mark(2);
+    RsArgs a = gather_args<RsArgs>(view, r, pr, n_objects, o.base, nw);
+    a.nh = o.base.nh;
+    a.pp2 = rs_pp2(view, o.point_pixels);
+    for (int k = 0; k < 3; ++k) a.cn[k] = cn[k];
+    hip_check(launch_reproject_spec(a, ng, pg, pb.c0, d_reusable, d_through, nw.fresh, nw.pxs, nb.c0, nb.c1, stream),
+              "reproject_spec_kernel");
+    mark(3);
+    const int n = r.width * r.height;
+    if (want_hist) hip_check(launch_denoise_unpack(nb.c0, n, nb.nrm(), nullptr, nb.dist(), stream), "denoise_unpack_kernel");
+    if (nw.fresh && (want_rad || want_u8))
+        hip_check(launch_denoise_unpack(nb.c1, n, want_rad ? nb.rad() : nullptr, want_u8 ? nb.u8.p : nullptr, nullptr, stream),
+                  "denoise_unpack_kernel");
+    if (want_kind) hip_check(launch_reproject_spec_kind(nb.c1, n, d_kind, stream), "reproject_spec_kind_kernel");
+    mark(4);
+}
+
+// A call's outputs into the caller's arrays, then its one host sync.
+static void rs_outputs(const DnBufs& nb, const uint8_t* d_kind, const RegionIo& io, float* history, float* weight,
+                       float* radiance, uint8_t* rgb, uint8_t* kind) {
+    io.down(history, nb.nrm(), 3 * sizeof(float));
+    io.down(weight, nb.dist(), sizeof(float));
+    io.down(radiance, nb.rad(), 3 * sizeof(float));
+    io.down(rgb, nb.u8, 3);
+    io.down(kind, d_kind, 1);
+    hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
+}
+
+// The previous view's side of a camera call, on the current device: its context with the radiance
+// uploaded into rp_prev.rad() and both guide passes queued into rp_prev.gn / gp and rs_prev.
+static RsGuides rs_prev_side(rt_camera* prev_cam, const rt_region& pr, const float* prev_radiance,
+                             const rt_guide_options& go, hipStream_t stream, hipEvent_t* ev,
+                             const std::function<void()>& new_guides) {
+    DevCtx& p = prev_cam->current();
+    p.ensure_device();
+    DnBufs& pb = p.rp_prev;
+    const size_t n = (size_t)pr.width * pr.height;
+    pb.ensure(n);
+    p.rs_prev.ensure(n);
+    RegionIo{prev_cam->build.cam.width, pr, stream}.up(pb.rad(), prev_radiance, 3 * sizeof(float));
+    hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
+    new_guides();
+    p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{pb.gn, pb.gp}, stream);
+    p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{p.rs_prev.sgn, p.rs_prev.sgp}, stream, &go, p.rs_prev.chain);
+    hip_check(hipEventRecord(ev[1], stream), "hipEventRecord");
+    return RsGuides{pb.gn, pb.gp, p.rs_prev.sgn, p.rs_prev.sgp, p.rs_prev.chain};
+}
+
+extern "C" {
+
+void rt_specular_reproject_options_default(rt_specular_reproject_options* options) {
+    if (options) *options = rt_specular_reproject_options{{0.9f, 0.01f, 0.25f, 32.0f}, 4.0f, 15};
+}
+
+int rt_camera_through_objects(const rt_camera* cam, int32_t mask, float max_fuzz, uint8_t* out, int32_t capacity) {
+    if (!cam || !out) return set_error(RT_ERR_INVALID, "null argument");
+    return api_guard([&] {
+        through_check("rt_camera_through_objects", mask, max_fuzz);
+        const std::vector<uint8_t> t = through_objects(*cam, mask, max_fuzz);
+        if ((int64_t)capacity < (int64_t)t.size())
+            throw std::invalid_argument("rt_camera_through_objects: capacity below the number of objects");
+        if (!t.empty()) std::memcpy(out, t.data(), t.size());
+    });
+}
+
+int rt_reproject_specular(int32_t width, int32_t height, const rt_region* region, const float* normal,
+                          const float* position, const float* distance, const int32_t* object,
+                          const float* chain_normal, const float* chain_position, const float* chain_distance,
+                          const int32_t* chain_object, const int32_t* chain, const rt_view* view,
+                          const rt_view* prev_view, const rt_region* prev_region, const float* prev_radiance,
+                          const float* prev_normal, const float* prev_position, const float* prev_distance,
+                          const int32_t* prev_object, const float* prev_chain_normal, const float* prev_chain_position,
+                          const float* prev_chain_distance, const int32_t* prev_chain_object, const int32_t* prev_chain,
+                          const uint8_t* reusable, const uint8_t* through, int32_t n_objects,
+                          const rt_specular_reproject_options* options, const float* radiance, const int32_t* px_samples,
+                          int32_t samples, float* history_out, float* weight_out, float* radiance_out, uint8_t* rgb_out,
+                          uint8_t* kind_out) {
+    return api_guard([&] {
+        const std::string who = "rt_reproject_specular";
+        if (width <= 0 || height <= 0) throw std::invalid_argument(who + ": width and height must be positive");
+        if (!normal || !position || !distance || !object)
+            throw std::invalid_argument(who + ": normal, position, distance and object are required");
+        if (!chain_normal || !chain_position || !chain_distance || !chain_object || !chain)
+            throw std::invalid_argument(who + ": chain_normal, chain_position, chain_distance, chain_object and chain are required");
+        if (!view) throw std::invalid_argument(who + ": view is required");
+        if (!prev_view || !prev_normal || !prev_position || !prev_distance || !prev_object)
+            throw std::invalid_argument(who + ": prev_view, prev_normal, prev_position, prev_distance and prev_object are required");
+        if (!prev_chain_normal || !prev_chain_position || !prev_chain_distance || !prev_chain_object || !prev_chain)
+            throw std::invalid_argument(who + ": prev_chain_normal, prev_chain_position, prev_chain_distance, "
+                                              "prev_chain_object and prev_chain are required");
+        if (prev_view->width <= 0 || prev_view->height <= 0)
+            throw std::invalid_argument(who + ": the previous view's width and height must be positive");
+        if (n_objects < 0 || (n_objects > 0 && (!reusable || !through)))
+            throw std::invalid_argument(who + ": reusable and through must hold n_objects >= 0 entries");
+        rp_check(who, prev_radiance, radiance, samples, radiance_out, rgb_out);
+        const RsOpts o = rs_resolve(options, who);
+        const hipStream_t stream = nullptr;
+        const RegionIo io{width, dn_region(region, width, height, who), stream};
+        const RegionIo pio{prev_view->width, dn_region(prev_region, prev_view->width, prev_view->height, who), stream};
+        const RpView pv = rp_view_constants(prev_view->center, prev_view->pixel00, prev_view->du, prev_view->dv,
+                                            prev_view->width, prev_view->height);
+        // (ns / ps: the chain guides' pairs, their obj planes the chain words, ns.u8 the kind plane)
+        DnBufs nb, pb, ns, ps;
+        DevBuf<uint8_t> d_reusable, d_through;
+        nb.ensure((size_t)io.n());
+        ns.ensure((size_t)io.n());
+        pb.ensure((size_t)pio.n());
+        ps.ensure((size_t)pio.n());
+        upload_reusable(d_reusable, reusable, n_objects, stream);
+        upload_reusable(d_through, through, n_objects, stream);
+        upload_guides(nb, io, normal, position, distance, object);
+        upload_guides(ns, io, chain_normal, chain_position, chain_distance, chain_object);
+        upload_guides(pb, pio, prev_normal, prev_position, prev_distance, prev_object);
+        upload_guides(ps, pio, prev_chain_normal, prev_chain_position, prev_chain_distance, prev_chain_object);
+        // (the guides are packed: the staging arrays now carry the chain words, the frames and the counts)
+        io.up(ns.obj, chain, sizeof(int32_t));
+        pio.up(ps.obj, prev_chain, sizeof(int32_t));
+        pio.up(pb.rad(), prev_radiance, 3 * sizeof(float));
+        if (radiance) io.up(nb.rad(), radiance, 3 * sizeof(float));
+        if (radiance && px_samples) io.up(nb.obj, px_samples, sizeof(int32_t));
+        const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
+                       io.r.width, 0, 0, (float)samples};
+        const RsGuides ng{nb.gn, nb.gp, ns.gn, ns.gp, ns.obj}, pg{pb.gn, pb.gp, ps.gn, ps.gp, ps.obj};
+        rs_run(nb, pb, ng, pg, ns.u8, pv, view->center, io.r, pio.r, d_reusable, d_through, n_objects, o, nw,
+               history_out || weight_out, radiance_out != nullptr, rgb_out != nullptr, kind_out != nullptr, stream, nullptr);
+        rs_outputs(nb, ns.u8, io, history_out, weight_out, radiance_out, rgb_out, kind_out);
+    });
+}
+
+int rt_camera_reproject_specular(rt_camera* cam, const rt_region* region, rt_camera* prev_cam,
+                                 const rt_region* prev_region, const rt_guide_options* guide_options_,
+                                 const rt_specular_reproject_options* options, const float* prev_radiance,
+                                 const float* radiance, const int32_t* px_samples, int32_t samples, float* history_out,
+                                 float* weight_out, float* radiance_out, uint8_t* rgb_out, uint8_t* kind_out) {
+    return two_camera_call(cam, prev_cam, [&] {
+        const std::string who = "rt_camera_reproject_specular";
+        const RtCamera &C = cam->build.cam, &PC = prev_cam->build.cam;
+        rp_check(who, prev_radiance, radiance, samples, radiance_out, rgb_out);
+        const RsOpts o = rs_resolve(options, who);
+        const rt_guide_options go = rs_guide_options(guide_options_, who);
+        const hipStream_t stream = nullptr;
+        const RegionIo io{C.width, dn_region(region, C.width, C.height, who), stream};
+        const rt_region pr = dn_region(prev_region, PC.width, PC.height, who);
+        rp_same_scene(cam, prev_cam);
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        DnBufs& nb = c.dn;
+        nb.ensure((size_t)io.n());
+        c.rs.ensure((size_t)io.n());
+        hipEvent_t* ev = c.rp_events();
+        const uint8_t* d_reusable = c.ensure_reusable();
+        const uint8_t* d_through = ensure_through(c, o.through, go.max_fuzz);
+        if (radiance) io.up(nb.rad(), radiance, 3 * sizeof(float));
+        if (radiance && px_samples) io.up(nb.obj, px_samples, sizeof(int32_t));
+        const RsGuides pg = rs_prev_side(prev_cam, pr, prev_radiance, go, stream, ev, [&] {
+            c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{nb.gn, nb.gp}, stream);
+            c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{c.rs.sgn, c.rs.sgp}, stream, &go, c.rs.chain);
+        });
+        const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
+                       io.r.width, 0, 0, (float)samples};
+        const RsGuides ng{nb.gn, nb.gp, c.rs.sgn, c.rs.sgp, c.rs.chain};
+        rs_run(nb, prev_cam->current().rp_prev, ng, pg, c.rs.kind, rp_camera_view(prev_cam), C.center, io.r, pr, d_reusable,
+               d_through, C.n_prims, o, nw, history_out || weight_out, radiance_out != nullptr, rgb_out != nullptr,
+               kind_out != nullptr, stream, ev);
+        c.rp_timed = true;
+        rs_outputs(nb, c.rs.kind, io, history_out, weight_out, radiance_out, rgb_out, kind_out);
+    });
+}
+
+int rt_camera_progressive_reproject_specular(rt_camera* cam, rt_camera* prev_cam, const rt_region* prev_region,
+                                             const rt_guide_options* guide_options_,
+                                             const rt_specular_reproject_options* options, const float* prev_radiance,
+                                             uint8_t* rgb, float* radiance, float* weight_out, uint8_t* kind_out) {
+    return two_camera_call(cam, prev_cam, [&] {
+        const std::string who = "rt_camera_progressive_reproject_specular";
+        (void)cam->session(who.c_str());
+        session_radiance(cam, who);
+        rp_check(who, prev_radiance, nullptr, 0, nullptr, nullptr);
+        const RsOpts o = rs_resolve(options, who);
+        const rt_guide_options go = rs_guide_options(guide_options_, who);
+        const RtCamera &C = cam->build.cam, &PC = prev_cam->build.cam;
+        const rt_region pr = dn_region(prev_region, PC.width, PC.height, who);
+        rp_same_scene(cam, prev_cam);
+        DevCtx& c = session_with(cam, who, 0);
+        DevCtx::ProgSession& P = c.prog;
+        const hipStream_t stream = nullptr;
+        const RegionIo io{C.width, P.region, stream};
+        DnBufs& nb = c.dn;
+        nb.ensure((size_t)io.n());
+        c.rs.kind.ensure((size_t)io.n(), "hipMalloc(chain guides)");
+        hipEvent_t* ev = c.rp_events();
+        const uint8_t* d_reusable = c.ensure_reusable();
+        const uint8_t* d_through = ensure_through(c, o.through, go.max_fuzz);
+        const RsGuides pg = rs_prev_side(prev_cam, pr, prev_radiance, go, stream, ev, [&] {
+            session_guides(cam, c, stream);
+            session_specular_guides(cam, c, go, stream, true);
+        });
+        const RpNew nw{P.d_gn, P.d_gp, P.d_rad, P.d_pxs, C.width, io.r.x, io.r.y, 0.0f};
+        const RsGuides ng{P.d_gn, P.d_gp, P.d_sgn, P.d_sgp, P.d_sch};
+        rs_run(nb, prev_cam->current().rp_prev, ng, pg, c.rs.kind, rp_camera_view(prev_cam), C.center, io.r, pr, d_reusable,
+               d_through, C.n_prims, o, nw, weight_out != nullptr, radiance != nullptr, rgb != nullptr, kind_out != nullptr,
+               stream, ev);
+        c.rp_timed = true;
+        rs_outputs(nb, c.rs.kind, io, nullptr, weight_out, radiance, rgb, kind_out);
+    });
+}
+
+}  // extern "C"

@@ -17,21 +17,23 @@ per-pixel variance map (ProgressiveRender.variance, progressive_blob_variance) g
 when `variance=` is passed to any of them, and `guides="specular"` /
 render_guides(through_specular=True) take the guides behind mirrors and glass. A previous view's frame is reprojected into a moved
 camera's view by Camera.reproject / reproject / ProgressiveRender.reprojected (Camera.view,
-Camera.reusable_objects), so the first frames of a new view start from the last view's history. A History follows a camera
+Camera.reusable_objects), so the first frames of a new view start from the last view's history;
+with `guides="specular"` (reproject_specular, Camera.through_objects) what a mirror or glass shows
+finds its history too. A History follows a camera
 along a path on the device: ProgressiveRender.accumulated blends each view's frame onto it by
 per-pixel history lengths and carries a variance the variance-guided filter consumes
 (temporal_accumulate: the same with explicit buffers). Vary `seed` per view.
 """
 from ._lib import RtError, build_id, device_count, progressive_blob_info, progressive_blob_variance
-from .camera import (Camera, History, ProgressiveRender, RenderStats, denoise, reproject, rng_stream,
-                     temporal_accumulate)
+from .camera import (Camera, History, ProgressiveRender, RenderStats, denoise, reproject, reproject_specular,
+                     rng_stream, temporal_accumulate)
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
                      generate_scene_data, generateScene, generateSceneData)
 
 __all__ = [
     "Camera", "ProgressiveRender", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
-    "progressive_blob_info", "progressive_blob_variance", "denoise", "reproject", "History",
+    "progressive_blob_info", "progressive_blob_variance", "denoise", "reproject", "reproject_specular", "History",
     "temporal_accumulate",
     "generate_scene_data", "create_camera_from_scene_data", "generate_scene",
     "generate_image_buffer", "divide_into_regions",

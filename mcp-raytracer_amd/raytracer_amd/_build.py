@@ -57,6 +57,9 @@ _UNITS = [
     # the reprojection gather: as the filter, every fp32 operation rounds once - the output equals
     # tests/reproject_ref.py in every bit
     ("reproject.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the reprojection gather through specular chains: the same rule - the output equals
+    # tests/specular_reproject_ref.py in every bit
+    ("reproject_spec.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the accumulation across views: the same rule - the output equals tests/temporal_ref.py in
     # every bit
     ("temporal.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
@@ -77,6 +80,9 @@ _UNITS = [
     ("pass_host.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("api_denoise.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("api_reproject.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    # the ABI unit of the reprojection through specular chains, with the api_* units' flags: its
+    # pp2 is a host computation that must not be contracted
+    ("reproject_spec_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("api_temporal.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("api_focus.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("dev_ctx.cpp", ["-ffp-contract=off", "-x", "hip"], True),
@@ -91,7 +97,7 @@ _UNITS = [
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
             "pt_brute.hpp", "pt_shade.hpp", "pt_pixel.hpp", "pt_kernels.hpp", "pt_pool.hpp", "pt_dispatch.hpp",
             "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "reproject.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp", "api_call.hpp", "pass_host.hpp"]
 _LIBS = ["-lz"]
 

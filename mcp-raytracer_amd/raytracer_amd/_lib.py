@@ -118,6 +118,10 @@ class RtReprojectOptions(C.Structure):
                 ("history_samples", C.c_float)]
 
 
+class RtSpecularReprojectOptions(C.Structure):
+    _fields_ = [("base", RtReprojectOptions), ("point_pixels", C.c_float), ("through", C.c_int32)]
+
+
 class RtTemporalOptions(C.Structure):
     _fields_ = [("normal_min", C.c_float), ("sigma_plane", C.c_float), ("min_weight", C.c_float),
                 ("max_history", C.c_float), ("filter_levels", C.c_int32), ("sigma_variance", C.c_float)]
@@ -279,6 +283,21 @@ _SIGS = {
                                                   C.c_void_p]),
     "rt_camera_reproject_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_float)]),
+    "rt_specular_reproject_options_default": (None, [C.POINTER(RtSpecularReprojectOptions)]),
+    "rt_camera_through_objects": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32]),
+    "rt_reproject_specular": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), *[C.c_void_p] * 9, C.POINTER(RtView),
+                                        C.POINTER(RtView), C.POINTER(RtRegion), *[C.c_void_p] * 10, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.POINTER(RtSpecularReprojectOptions), C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "rt_camera_reproject_specular": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.c_void_p, C.POINTER(RtRegion),
+                                               C.POINTER(RtGuideOptions), C.POINTER(RtSpecularReprojectOptions),
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_progressive_reproject_specular": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtRegion),
+                                                           C.POINTER(RtGuideOptions),
+                                                           C.POINTER(RtSpecularReprojectOptions), C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_history_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rt_history_destroy": (None, [C.c_void_p]),
     "rt_history_get_info": (C.c_int, [C.c_void_p, C.POINTER(RtHistoryInfo)]),

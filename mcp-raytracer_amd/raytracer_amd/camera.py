@@ -268,6 +268,76 @@ def reproject(prev_radiance, prev_view, prev_guides, *, normal, position, distan
     return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
 
 
+def _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, through):
+    """rt_specular_reproject_options (a zero field = the default; the library validates the rest)."""
+    return _lib.RtSpecularReprojectOptions(_reproject_options(normal_min, sigma_plane, min_weight, history_samples),
+                                           float(point_pixels), int(through))
+
+
+def _kind_out(kind, shape):
+    """Pointer of the optional caller-owned (H, W) uint8 array the kind plane goes to."""
+    import numpy as np
+    return _out_array(kind, np.uint8, shape, "kind")
+
+
+def _c_view(view) -> _lib.RtView:
+    import numpy as np
+    v = _lib.RtView()
+    for k in ("center", "pixel00", "du", "dv"):
+        getattr(v, k)[:] = [float(x) for x in np.asarray(view[k], dtype=np.float32)]
+    v.width, v.height = int(view["width"]), int(view["height"])
+    return v
+
+
+def reproject_specular(prev_radiance, prev_view, prev_first, prev_chain, view, first, chain, reusable, through, *,
+                       region=None, prev_region=None, radiance=None, px_samples=None, samples=None, rgb=None, out=None,
+                       history_out=None, weight_out=None, kind=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25,
+                       history_samples=32.0, point_pixels=4.0):
+    """rt_reproject_specular: reproject() through specular chains, explicit buffers, no camera.
+    first / prev_first: the new and the previous view's first-hit guides as Camera.render_guides()
+    returns them; chain / prev_chain: their guides through the chain, render_guides(
+    through_specular=True) of one max_bounces / max_fuzz (with "chain"); view: the new camera's
+    Camera.view(); reusable / through: uint8 per object, as Camera.reusable_objects() and
+    Camera.through_objects(). A pixel whose chain has length 0 is reproject()'s; a pixel that shows a
+    lambert or light surface through a chain finds its history at the chain's virtual point. `kind`
+    (optional uint8 (H, W)) receives 0 no history, 1 first hit, 2 chain. Everything else as
+    reproject(). Equals tests/specular_reproject_ref.py in every bit."""
+    import numpy as np
+    obj = np.asarray(first["object"])
+    if obj.ndim != 2:
+        raise ValueError("object must have shape (H, W)")
+    H, W = obj.shape
+    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
+
+    def planes(g, h, w, with_chain):
+        a = [_f32_frame(g["normal"], (h, w, 3), "normal"), _f32_frame(g["position"], (h, w, 3), "position"),
+             _f32_frame(g["distance"], (h, w), "distance"), _f32_frame(g["object"], (h, w), "object")]
+        if with_chain:
+            a.append(_f32_frame(g["chain"], (h, w), "object"))
+        return a
+    g = planes(first, H, W, False) + planes(chain, H, W, True)
+    pg = planes(prev_first, Hp, Wp, False) + planes(prev_chain, Hp, Wp, True)
+    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
+    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
+    thr = np.ascontiguousarray(through, dtype=np.uint8).ravel()
+    if thr.size != reus.size:
+        raise ValueError("reusable and through must hold one entry per object")
+    rad, radp, pxsp, ns, res, resp, uptr, hist, histp, wptr, _keep = _reproject_frames(
+        H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
+    reg = None if region is None else _region(region)
+    preg = None if prev_region is None else _region(prev_region)
+    opts = _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, 0)
+    v, pv = _c_view(view), _c_view(prev_view)
+    _lib.check(_lib.load().rt_reproject_specular(
+        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], C.byref(v), C.byref(pv),
+        C.byref(preg) if preg is not None else None, prad.ctypes.data, *[a.ctypes.data for a in pg],
+        reus.ctypes.data if reus.size else None, thr.ctypes.data if thr.size else None, int(reus.size), C.byref(opts),
+        radp, pxsp, ns, histp, wptr, resp, uptr, _kind_out(kind, (H, W))))
+    if res is None:
+        return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
+    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+
 def _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance):
     """rt_temporal_options (a zero field = the default; the library validates the rest)."""
     return _lib.RtTemporalOptions(float(normal_min), float(sigma_plane), float(min_weight), float(max_history),
@@ -731,9 +801,20 @@ class Camera:
         _lib.check(self._lib.rt_camera_reusable_objects(self._h, out.ctypes.data, int(out.size)))
         return out[:self._info.n_objects]
 
+    def through_objects(self, mask: int = 15, max_fuzz: float = 0.0):
+        """rt_camera_through_objects: uint8 per SceneData.objects entry, 1 where the object's resolved
+        material class is in `mask` (1 a metal of fuzz <= max_fuzz, 2 glass, 4 mixed, 8 layered) -
+        the surfaces a reprojection through specular chains may start a chain on."""
+        import numpy as np
+        out = np.zeros(max(self._info.n_objects, 1), np.uint8)
+        _lib.check(self._lib.rt_camera_through_objects(self._h, int(mask), float(max_fuzz), out.ctypes.data,
+                                                       int(out.size)))
+        return out[:self._info.n_objects]
+
     def reproject(self, prev_cam: "Camera", prev_radiance, region=None, prev_region=None, radiance=None,
                   px_samples=None, samples=None, rgb=None, out=None, history_out=None, weight_out=None, *,
-                  normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0):
+                  normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0, guides=None,
+                  point_pixels=4.0, through=15, kind=None):
         """rt_camera_reproject: `prev_radiance` (float32 (Hp, Wp, 3), a frame of `prev_cam`, a camera
         of the same scene) reprojected into this camera's view; both views' guides are computed on
         the device. With a fresh `radiance` of this camera and its sample counts (`px_samples`
@@ -742,7 +823,14 @@ class Camera:
         optional float32 arrays; only the region is written. Equals reproject(prev_radiance,
         prev_cam.view(), prev_cam.render_guides(), reusable=self.reusable_objects(),
         **self.render_guides(), ...). The result can be fed to denoise() and chained as the next
-        call's prev_radiance."""
+        call's prev_radiance.
+
+        `guides="specular"` (or a dict of max_bounces / max_fuzz) runs rt_camera_reproject_specular
+        instead: pixels that show a lambert or light surface through mirrors or glass find their
+        history at the chain's virtual point, within `point_pixels` footprints, where the chain
+        starts on an object of `through_objects(through, max_fuzz)`; `kind` (optional uint8 (H, W))
+        receives 0 no history, 1 first hit, 2 chain. Equals reproject_specular() on both cameras'
+        guides. Without `guides=` the three keywords must be left alone."""
         H, W = self.image_height, self.image_width
         Hp, Wp = prev_cam.image_height, prev_cam.image_width
         prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
@@ -750,10 +838,20 @@ class Camera:
             H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
         reg = None if region is None else _region(region)
         preg = None if prev_region is None else _region(prev_region)
-        opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
-        _lib.check(self._lib.rt_camera_reproject(self._h, C.byref(reg) if reg is not None else None, prev_cam._h,
-                                                 C.byref(preg) if preg is not None else None, C.byref(opts),
-                                                 prad.ctypes.data, radp, pxsp, ns, histp, wptr, resp, uptr))
+        rptr = C.byref(reg) if reg is not None else None
+        pptr = C.byref(preg) if preg is not None else None
+        if guides is None:
+            if kind is not None or point_pixels != 4.0 or through != 15:
+                raise ValueError("kind, point_pixels and through need guides=")
+            opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+            _lib.check(self._lib.rt_camera_reproject(self._h, rptr, prev_cam._h, pptr, C.byref(opts), prad.ctypes.data,
+                                                     radp, pxsp, ns, histp, wptr, resp, uptr))
+        else:
+            go = _guide_options(guides)
+            opts = _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, through)
+            _lib.check(self._lib.rt_camera_reproject_specular(self._h, rptr, prev_cam._h, pptr, C.byref(go),
+                                                              C.byref(opts), prad.ctypes.data, radp, pxsp, ns, histp,
+                                                              wptr, resp, uptr, _kind_out(kind, (H, W))))
         if res is None:
             return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
         return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
@@ -948,14 +1046,18 @@ class ProgressiveRender:
         return radiance
 
     def reprojected(self, prev_cam: Camera, prev_radiance, rgb=None, radiance=None, weight_out=None, *,
-                    prev_region=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0):
+                    prev_region=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0,
+                    guides=None, point_pixels=4.0, through=15, kind=None):
         """The session's frame as it stands after the last step, blended with `prev_radiance`
         (float32 (Hp, Wp, 3), a frame of `prev_cam`, a camera of the same scene) reprojected into
         this view, every pixel weighted by its own sample count (rt_camera_progressive_reproject):
         only the previous radiance is uploaded, and the session itself is not touched. `rgb` (u8
         W*H*3), `radiance` (float32 W*H*3) and `weight_out` (float32 (H, W)) are optional
         caller-owned full-frame buffers; only the region is written. Returns the blend as a
-        (H, W, 3) array (`radiance` when given; else a new one, zero outside the region)."""
+        (H, W, 3) array (`radiance` when given; else a new one, zero outside the region).
+        `guides`, `point_pixels`, `through` and `kind` as in Camera.reproject
+        (rt_camera_progressive_reproject_specular): the session keeps the chain guides and their
+        chain plane beside its first-hit ones; its state and checkpoint bytes are not touched."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
         import numpy as np
@@ -968,10 +1070,19 @@ class ProgressiveRender:
         rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
         wptr = _out_array(weight_out, np.float32, shape[:2], "weight_out")
         preg = None if prev_region is None else _region(prev_region)
-        opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
-        _lib.check(cam._lib.rt_camera_progressive_reproject(cam._h, prev_cam._h,
-                                                            C.byref(preg) if preg is not None else None,
-                                                            C.byref(opts), prad.ctypes.data, ptr, rptr, wptr))
+        pptr = C.byref(preg) if preg is not None else None
+        if guides is None:
+            if kind is not None or point_pixels != 4.0 or through != 15:
+                raise ValueError("kind, point_pixels and through need guides=")
+            opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+            _lib.check(cam._lib.rt_camera_progressive_reproject(cam._h, prev_cam._h, pptr, C.byref(opts),
+                                                                prad.ctypes.data, ptr, rptr, wptr))
+        else:
+            go = _guide_options(guides)
+            opts = _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, through)
+            _lib.check(cam._lib.rt_camera_progressive_reproject_specular(
+                cam._h, prev_cam._h, pptr, C.byref(go), C.byref(opts), prad.ctypes.data, ptr, rptr, wptr,
+                _kind_out(kind, shape[:2])))
         if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
             return radiance.reshape(shape)
         return radiance
