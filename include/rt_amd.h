@@ -165,6 +165,12 @@ int rt_camera_export(const rt_camera* cam, void* nodes, void* prims, void* mater
 int rt_debug_world_hit(rt_camera* cam, int32_t traversal, int32_t n, const float* orig, const float* dir,
                        double* out);
 
+/* rt_debug_world_hit through the fp32 build (precision "fp32": the fp32 intersectors, radius
+ * and plane constants, and the hit record as the fp32 path kernels form it), whatever the
+ * camera's precision. Same arguments and layout; t, p and n are fp32 values widened to double. */
+int rt_debug_world_hit_fp32(rt_camera* cam, int32_t traversal, int32_t n, const float* orig, const float* dir,
+                            double* out);
+
 /* The device's Math.cos(phi), Math.sin(phi) (phi = 2 PI xi, the cosine-PDF angle)
  * and Math.pow(xi, 5) (Schlick) for xi = u[k] / 2^32: out = host double[3*n]. */
 int rt_debug_math(int32_t n, const uint32_t* u, double* out);

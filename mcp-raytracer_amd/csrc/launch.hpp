@@ -61,6 +61,9 @@ hipError_t launch_init_stats(unsigned long long* stats, unsigned long long* coun
 // Closest hit through the device traversal for a batch of rays (parity tests).
 hipError_t launch_world_hit_ref(const DevScene& S, int trav, int n, const float* orig, const float* dir,
                                 double* out, hipStream_t stream);
+// The same through the fp32 build's intersectors and hit record (pt_probe_fp32.hip).
+hipError_t launch_world_hit_fp32(const DevScene& S, int trav, int n, const float* orig, const float* dir,
+                                 double* out, hipStream_t stream);
 
 // Device transcendental probe (V8 fixture tests): out[3k..3k+2] = cos, sin of 2 pi xi, pow(xi, 5).
 hipError_t launch_math_probe(int n, const uint32_t* u, double* out, hipStream_t stream);

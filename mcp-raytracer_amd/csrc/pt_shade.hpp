@@ -283,6 +283,19 @@ __device__ __forceinline__ V3 miss_color(const RtCamera& C, const Path<EMIT>& P,
     return c;
 }
 
+// A sphere's hit normal: Vec3.divide(radius) of p - center (sphere.ts:72). The fp32 build then
+// normalises the quotient: with p = o + t d and t rounded to fp32 it is off unit length by up
+// to 5e-4 on a small sphere a few units away, and reflect, refract and the
+// cosine PDF take a unit normal. The ref build keeps the reference's quotient bit for bit.
+// v_rsq_f32 (<= 1 ulp; |n|^2 is within 1e-3 of 1, far from its denormal range) leaves |n|^2
+// within 4e-7 of 1; the IEEE 1 / sqrt cost fp32 Cornell 1.0 % and spheres-500 0.6 %.
+template <class Real>
+__device__ __forceinline__ V3 sphere_normal(const RtPrim& pr, V3 p) {
+    const V3 n = scale<Real>(sub(p, ld3(pr.g0)), sphere_inv_radius<Real>(pr));
+    if constexpr (sizeof(Real) == 4) return scale<Real>(n, __builtin_amdgcn_rsqf(len2<Real>(n)));
+    else return n;
+}
+
 // Hit record (sphere.ts:67-84, quad.ts:72-83, plane.ts:246-259) and the
 // material's emission and scatter (camera.ts:246-262). Returns the scatter kind;
 // `planar` = the primitive has a fixed normal (quad / plane: ONB table lookup).
@@ -295,7 +308,7 @@ __device__ __forceinline__ int shade_hit(const DevScene& S, Path<EMIT>& P, int h
     p = ray_at<Real>(P.o, P.d, t);
     planar = pr.type != PRIM_SPHERE;
     if (!planar) {
-        nrm = scale<Real>(sub(p, ld3(pr.g0)), sphere_inv_radius<Real>(pr));  // Vec3.divide(radius)
+        nrm = sphere_normal<Real>(pr, p);
         front = dot<Real>(P.d, nrm) <= (Real)0;
         if (!front) nrm = neg(nrm);
     } else {

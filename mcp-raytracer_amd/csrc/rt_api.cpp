@@ -308,8 +308,9 @@ int rt_camera_export(const rt_camera* cam, void* nodes, void* prims, void* mater
     return RT_OK;
 }
 
-int rt_debug_world_hit(rt_camera* cam, int32_t traversal, int32_t n, const float* orig, const float* dir,
-                       double* out) {
+namespace {
+int debug_world_hit(rt_camera* cam, int prec, int32_t traversal, int32_t n, const float* orig, const float* dir,
+                    double* out) {
     if (!cam || n < 0 || (n > 0 && (!orig || !dir || !out))) return set_error(RT_ERR_INVALID, "bad arguments");
     std::lock_guard<std::mutex> lock(cam->mu);
     float* d_o = nullptr;
@@ -325,7 +326,8 @@ int rt_debug_world_hit(rt_camera* cam, int32_t traversal, int32_t n, const float
         hip_check(hipMemcpy(d_o, orig, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
         hip_check(hipMemcpy(d_d, dir, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
         const int trav = c.effective_traversal(traversal < 0 ? cam->traversal : traversal);
-        hip_check(launch_world_hit_ref(c.dev_scene(), trav, n, d_o, d_d, d_out, nullptr),
+        hip_check((prec == PREC_FP32 ? launch_world_hit_fp32 : launch_world_hit_ref)(c.dev_scene(), trav, n, d_o, d_d,
+                                                                                     d_out, nullptr),
                   "world_hit_kernel");
         hip_check(hipMemcpy(out, d_out, (size_t)n * 10 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy");
         (void)hipFree(d_o);
@@ -338,6 +340,17 @@ int rt_debug_world_hit(rt_camera* cam, int32_t traversal, int32_t n, const float
         if (d_out) (void)hipFree(d_out);
         return set_error(RT_ERR_DEVICE, e.what());
     }
+}
+}  // namespace
+
+int rt_debug_world_hit(rt_camera* cam, int32_t traversal, int32_t n, const float* orig, const float* dir,
+                       double* out) {
+    return debug_world_hit(cam, PREC_REF, traversal, n, orig, dir, out);
+}
+
+int rt_debug_world_hit_fp32(rt_camera* cam, int32_t traversal, int32_t n, const float* orig, const float* dir,
+                            double* out) {
+    return debug_world_hit(cam, PREC_FP32, traversal, n, orig, dir, out);
 }
 
 int rt_debug_math(int32_t n, const uint32_t* u, double* out) {

@@ -46,6 +46,9 @@ _KERNEL_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-disable-machine-licm"]
 _UNITS = [
     ("pt_ref.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     ("pt_fp32.hip", ["-ffp-contract=fast", *_KERNEL_FLAGS], True),
+    # the fp32 closest-hit probe (rt_debug_world_hit_fp32): pt_fp32.hip's flags, so it runs the
+    # fp32 path kernels' intersectors as they are compiled there
+    ("pt_probe_fp32.hip", ["-ffp-contract=fast", *_KERNEL_FLAGS], True),
     ("progressive.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # guide pass + a-trous filter, plain and variance-guided: every fp32 operation must round once
     # (no contraction; plain / and sqrtf are IEEE under hipcc's defaults) - the output equals

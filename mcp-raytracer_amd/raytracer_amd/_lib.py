@@ -201,6 +201,7 @@ _SIGS = {
     "rt_camera_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
     "rt_debug_world_hit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_debug_world_hit_fp32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_pass_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                      C.POINTER(C.c_int64)]),
     "rt_debug_scene_blob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RtSceneBlobInfo)]),

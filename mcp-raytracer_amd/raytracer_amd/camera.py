@@ -882,15 +882,16 @@ class Camera:
                                               prim_object.ctypes.data))
         return {"nodes": nodes, "prims": prims, "materials": mats, "lights": lights, "prim_object": prim_object}
 
-    def debug_world_hit(self, origins, directions, traversal: Optional[str] = None):
-        """Closest hit of rays through the device BVH (ref precision)."""
+    def debug_world_hit(self, origins, directions, traversal: Optional[str] = None, precision: str = "ref"):
+        """Closest hit of rays through the device BVH, in ref precision or through the fp32
+        build (rt_debug_world_hit_fp32): rows of {hit, t, p.xyz, n.xyz, front, prim slot}."""
         import numpy as np
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         out = np.zeros((o.shape[0], 10), dtype=np.float64)
         tr = -1 if traversal is None else _lib.TRAVERSAL[traversal]
-        _lib.check(self._lib.rt_debug_world_hit(self._h, tr, o.shape[0], o.ctypes.data, d.ctypes.data,
-                                                out.ctypes.data))
+        fn = self._lib.rt_debug_world_hit_fp32 if _lib.PRECISION[precision] == 1 else self._lib.rt_debug_world_hit
+        _lib.check(fn(self._h, tr, o.shape[0], o.ctypes.data, d.ctypes.data, out.ctypes.data))
         return out
 
     def close(self) -> None:

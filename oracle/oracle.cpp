@@ -1087,6 +1087,37 @@ int render_impl(const char* scene_json, const char* render_json, int rx, int ry,
     return 0;
 }
 
+template <class R>
+int world_hit_impl(const char* scene_json, int n, const float* orig, const float* dir, double tmin, double tmax,
+                   double* out) {
+    J sd = parse_json(scene_json);
+    auto cam = std::make_unique<Camera<R>>();
+    cam->load(sd, nullptr);
+    const Interval<R> iv{(R)tmin, (R)tmax};
+    for (int k = 0; k < n; k++) {
+        Ray<R> r;
+        for (int a = 0; a < 3; a++) { r.origin.v[a] = orig[k * 3 + a]; r.direction.v[a] = dir[k * 3 + a]; }
+        HitRecord<R> rec;
+        double* o = out + k * 10;
+        bool h = cam->scene.world->hit(r, iv, rec);
+        o[0] = h;
+        o[1] = h ? (double)rec.t : 0;
+        for (int a = 0; a < 3; a++) { o[2 + a] = h ? rec.p.v[a] : 0; o[5 + a] = h ? rec.normal.v[a] : 0; }
+        o[8] = h ? rec.frontFace : 0;
+        o[9] = -1;
+        if (h) {
+            for (size_t i = 0; i < cam->scene.objs.size(); i++) {
+                HitRecord<R> r2;
+                // identify by material pointer + t equality
+                if (cam->scene.objs[i]->hit(r, iv, r2) && r2.t == rec.t && r2.material == rec.material) {
+                    o[9] = (double)i; break;
+                }
+            }
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1113,35 +1144,20 @@ int or_render(const char* scene_json, const char* render_json, int rx, int ry, i
     }
 }
 
-// Closest hit through the oracle's recursive BVH for a batch of rays (ref mode).
+// Closest hit through the oracle's recursive BVH for a batch of rays.
 // out per ray: {hit, t, p.xyz, n.xyz, front, object_index}
 int or_world_hit(const char* scene_json, int n, const float* orig, const float* dir, double tmin, double tmax,
                  double* out) {
+    try { return world_hit_impl<double>(scene_json, n, orig, dir, tmin, tmax, out); }
+    catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// The same with real_kind as or_render's: 0 = ref (double scalars), 1 = fp32 (Scene<float>).
+int or_world_hit_kind(const char* scene_json, int n, const float* orig, const float* dir, double tmin, double tmax,
+                      int real_kind, double* out) {
     try {
-        J sd = parse_json(scene_json);
-        auto cam = std::make_unique<Camera<double>>();
-        cam->load(sd, nullptr);
-        for (int k = 0; k < n; k++) {
-            Ray<double> r;
-            for (int a = 0; a < 3; a++) { r.origin.v[a] = orig[k * 3 + a]; r.direction.v[a] = dir[k * 3 + a]; }
-            HitRecord<double> rec;
-            double* o = out + k * 10;
-            bool h = cam->scene.world->hit(r, Interval<double>{tmin, tmax}, rec);
-            o[0] = h;
-            o[1] = h ? rec.t : 0;
-            for (int a = 0; a < 3; a++) { o[2 + a] = h ? rec.p.v[a] : 0; o[5 + a] = h ? rec.normal.v[a] : 0; }
-            o[8] = h ? rec.frontFace : 0;
-            o[9] = -1;
-            if (h) {
-                for (size_t i = 0; i < cam->scene.objs.size(); i++) {
-                    HitRecord<double> r2;
-                    // identify by material pointer + t equality
-                    if (cam->scene.objs[i]->hit(r, Interval<double>{tmin, tmax}, r2) && r2.t == rec.t &&
-                        r2.material == rec.material) { o[9] = (double)i; break; }
-                }
-            }
-        }
-        return 0;
+        if (real_kind == 1) return world_hit_impl<float>(scene_json, n, orig, dir, tmin, tmax, out);
+        return world_hit_impl<double>(scene_json, n, orig, dir, tmin, tmax, out);
     } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
 

@@ -44,6 +44,8 @@ def load():
                                   C.c_void_p, C.c_void_p]
         lib.or_world_hit.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                      C.c_void_p]
+        lib.or_world_hit_kind.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                          C.c_int, C.c_void_p]
         for name in ["or_sphere_hit"]:
             getattr(lib, name).argtypes = [D, C.c_double, D, D, C.c_double, C.c_double, D]
         lib.or_quad_hit.argtypes = [D, D, D, D, D, C.c_double, C.c_double, D]
@@ -128,12 +130,14 @@ def render(scene: dict, render_opts: dict | None = None, region=None, precision:
     return out
 
 
-def world_hit(scene: dict, origins, directions, tmin=0.001, tmax=float("inf")):
+def world_hit(scene: dict, origins, directions, tmin=0.001, tmax=float("inf"), precision: str = "ref"):
+    """Closest hit of rays: rows of {hit, t, p.xyz, n.xyz, front, object index}; precision "fp32"
+    runs Scene<float> (t, p and n are then fp32 values)."""
     o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
     dr = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
     out = np.zeros((o.shape[0], 10), dtype=np.float64)
-    if load().or_world_hit(json.dumps(scene).encode(), o.shape[0], o.ctypes.data, dr.ctypes.data, tmin, tmax,
-                           out.ctypes.data):
+    if load().or_world_hit_kind(json.dumps(scene).encode(), o.shape[0], o.ctypes.data, dr.ctypes.data, tmin, tmax,
+                                1 if precision == "fp32" else 0, out.ctypes.data):
         raise _err()
     return out
 
