@@ -148,7 +148,7 @@ void DevCtx::times(float* path_ms, float* accum_ms) {
 DevScene DevCtx::dev_scene() const {
     DevScene S;
     const char* b = reinterpret_cast<const char*>(d_blob.p);
-    S.tnodes = reinterpret_cast<const RtTNode*>(b);
+    S.t4nodes = reinterpret_cast<const RtT4Node*>(b);
     S.prims = reinterpret_cast<const RtPrim*>(b + blob.off_prims);
     S.gprims = S.prims;
     S.gpre = reinterpret_cast<const RtPre*>(b + blob.off_pre);
@@ -179,8 +179,8 @@ DevScene DevCtx::dev_scene() const {
     S.n_top = 0;         // set per launch when the tree is walked from global memory
     S.top_lds = nullptr;
     S.nearfar = 0;       // (scene_view sets it per LDS level)
-    S.troot = build.t4root;
-    S.root_box = build.troot_box;
+    S.t4root = build.t4root;
+    S.root_box = build.t4root_box;
     S.cam = build.cam;
     S.mix_total = host.mix_total;
     S.light_w = host.light_w;

@@ -71,7 +71,7 @@ struct CamHost {
     rt_guide_options dn_guide{RT_GUIDES_FIRST_HIT, 8, 0.0f};
 
     // The strategy a launch actually uses: BRUTE/FAST are exact only where every
-    // primitive lies inside its reference box (scene.cpp prims_inside_boxes).
+    // primitive lies inside its reference box (scene_tree.cpp prims_inside_boxes).
     int effective_traversal(int trav) const {
         if (!build.fast_ok) return TRAV_REFERENCE;
         if (trav == TRAV_AUTO) return build.cam.n_prims <= kBruteMaxPrims ? TRAV_BRUTE : TRAV_FAST;
@@ -162,7 +162,7 @@ struct DevCtx {
     hipEvent_t pass_event(int p, int k);
 
     // The strategy a launch actually uses: BRUTE/FAST are exact only where every
-    // primitive lies inside its reference box (scene.cpp prims_inside_boxes).
+    // primitive lies inside its reference box (scene_tree.cpp prims_inside_boxes).
     int effective_traversal(int trav) const { return host.effective_traversal(trav); }
 
     // Device time of the last launch from its events: path kernel(s) and accumulate passes,

@@ -23,7 +23,7 @@ struct LaunchGeom {
     int lds_level;     // LDS-resident scene: 0 none, 1 traversal data + prims, 2 also mats + lights
 };
 
-// LDS budget (stack + [tnodes][prims]) up to which the scene is copied into LDS.
+// LDS budget (stack + [t4nodes] ... [xrec]) up to which the scene is copied into LDS.
 constexpr int kLdsSceneMaxBytes = 152 * 1024;
 // Static LDS of the chunked / pool kernels (the phase table), beside the dynamic allocation.
 constexpr size_t kStaticLdsBytes = 512;

@@ -29,7 +29,7 @@
 #include <cstdint>
 
 #include "rt_math.hpp"
-#include "scene.hpp"
+#include "scene_types.hpp"
 
 namespace rt {
 

@@ -47,7 +47,7 @@ __device__ __forceinline__ DevScene scene_view(const DevScene& S0, int* lds_stac
     if (LDSS > 0) {
         S.n_top = 0;  // the whole tree is in LDS (a constant: the walk's reads stay ds_read)
         const char* b = reinterpret_cast<const char*>(lds_stack) + S0.lds_stack_bytes;
-        S.tnodes = reinterpret_cast<const RtTNode*>(b);
+        S.t4nodes = reinterpret_cast<const RtT4Node*>(b);
         S.t4_stride = S0.lds_node_pad > 0 ? (int)sizeof(RtT4Node) + 16 : (int)sizeof(RtT4Node);
         b += (size_t)S0.lds_node_pad * 16;  // every section after the nodes moves by the pad rows
         S.tprims = reinterpret_cast<const int32_t*>(b + S0.off_tprims);

@@ -9,15 +9,17 @@
 #include <type_traits>
 
 #include "rt_math.hpp"
-#include "scene.hpp"
+#include "scene_types.hpp"
 
 namespace rt {
 
-// The scene lives in one device buffer ("blob"): [tnodes][tprims][tsph][prims][mats][lights][nodes],
-// 16-byte aligned sections. When [tnodes][prims] fits, every workgroup copies
-// it into LDS (LDS-resident launch): traversal and primitive reads are LDS reads.
+// The scene lives in one device buffer ("blob", scene_blob.cpp build_scene_blob):
+// [t4nodes][tprims][tsph][prims][xrec] | [mats][lights][onbs] | [nodes][pre][tsph2], 16-byte
+// aligned sections. When the first group fits beside the stack, every workgroup copies it into
+// LDS (LDS-resident launch, level 1): traversal and primitive reads are LDS reads; level 2 also
+// copies the second group.
 struct DevScene {
-    const RtTNode* __restrict__ tnodes; // fast traversal: children-in-parent nodes (blob start)
+    const RtT4Node* __restrict__ t4nodes; // fast traversal: 4-wide nodes (blob start; LDS when resident)
     const RtPrim* __restrict__ prims;   // global, or LDS in an LDS-resident launch
     const RtPrim* __restrict__ gprims;  // always the global copy (scalar-load reads)
     const RtPre* __restrict__ gpre;     // brute-force pre-filter records (global, scalar-load reads)
@@ -33,9 +35,9 @@ struct DevScene {
     const RtOnb* __restrict__ onbs;     // [slot][precision][face] for slots < n_onb (LDS at level 2)
     int32_t n_onb;                      // planar primitives' ONB table covers slots [0, n_onb)
     int32_t off_onbs;                   // byte offset of onbs in the blob
-    const uint4* __restrict__ blob;     // the whole scene: [tnodes][tprims][tsph][prims][mats][lights][nodes]
-    int32_t lds_words;                  // 16-byte words of the blob prefix copied to LDS (LDSS 1: [tnodes][tprims][tsph][prims],
-                                        // LDSS 2: also [mats][lights])
+    const uint4* __restrict__ blob;     // the whole scene (section order above)
+    int32_t lds_words;                  // 16-byte words of the blob prefix copied to LDS (LDSS 1: [t4nodes][tprims][tsph][prims][xrec],
+                                        // LDSS 2: also [mats][lights][onbs])
     int32_t off_prims;                  // byte offset of prims in the blob
     int32_t off_mats;                   // byte offset of mats in the blob
     int32_t off_lights;                 // byte offset of lights in the blob
@@ -52,7 +54,7 @@ struct DevScene {
                                          // the fp64 radius and the slot (one load per exact test), or null
     int32_t nearfar;                    // 4-wide node step picks near / far rows by the ray's signs (t4_step);
                                         // scene_view sets a constant per LDS level (see there)
-    int32_t troot;                      // fast traversal root reference
+    int32_t t4root;                     // fast traversal root reference (node index or leaf code)
     RtNode root_box;                    // fast traversal root box (padded)
     RtCamera cam;
     double mix_total;  // MixturePDF.totalWeight for [0.5, 0.5/nL x nL]

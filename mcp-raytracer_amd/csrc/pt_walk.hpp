@@ -58,7 +58,7 @@ __device__ __forceinline__ FRay make_fray(V3 o, V3 d) {
         // component, inv = 1e30, made eps ~1e24 and every box accepted). Their planes need no
         // absolute slack: the fused error is u|o_a inv_a| + relative terms, and for a face b
         // either |o_a| <= 4 (1 + |b|), where the box's outward padding of 1e-6 (1 + |b|)
-        // (scene.cpp make_fast_nodes) is >= 2u|o_a| in coordinates, so the padded face's computed
+        // (scene_tree.cpp make_fast_nodes) is >= 2u|o_a| in coordinates, so the padded face's computed
         // t stays outside the unpadded face's exact t; or |o_a| > 4 (1 + |b|), where
         // |t_a| = |b - o_a| |inv_a| >= 0.75 |o_a inv_a| and the error is relative, <= 2.7u |t_a|,
         // inside slab_accept's relative 2e-6 (~33u) with the rcp and fma roundings (~3u).
@@ -87,7 +87,7 @@ __device__ __forceinline__ FRay make_fray(V3 o, V3 d) {
 // final one, u = 2^-24. The acceptance test tn <= tf * 1.000002 + eps covers it: the u|t|
 // part is inside the relative 2e-6 (tn and tf are both positive whenever the box can hold a
 // hit, t > 0.001), the u|o * inv| part of either end inside eps = 1e-6 max_a |o_a inv_a|
-// (~16 u). On top of that every box is padded by 1e-6 (1 + |b|) (scene.cpp make_fast_nodes),
+// (~16 u). On top of that every box is padded by 1e-6 (1 + |b|) (scene_tree.cpp make_fast_nodes),
 // the margin the unfused test already relied on for the exact hit point.
 // A ray whose o * inv overflows gets inv = noi = 0, eps = inf: t = 0 on every plane (NaN
 // on an infinite bound, which fminf / fmaxf ignore), tf = min(thi, 0) >= 0, and the test
@@ -131,9 +131,9 @@ __device__ __forceinline__ bool slab(const RtNode& n, const R& f, float thi, flo
 // in LDS beside the stack (t4_step reads a node from there or from global memory: two loads in two
 // branches, so each stays a ds_read / global_load - one generic pointer made them flat loads,
 // 3.5 % slower on spheres-100k).
-// (a 24-bit multiply, full rate: node indices stay below 2^24, scene.cpp make_t4nodes)
+// (a 24-bit multiply, full rate: node indices stay below 2^24, scene_tree.cpp make_t4nodes)
 __device__ __forceinline__ const RtT4Node* t4_node(const DevScene& S, int ref) {
-    return reinterpret_cast<const RtT4Node*>(reinterpret_cast<const char*>(S.tnodes) +
+    return reinterpret_cast<const RtT4Node*>(reinterpret_cast<const char*>(S.t4nodes) +
                                              (size_t)__umul24((unsigned)ref, (unsigned)S.t4_stride));
 }
 struct T4Rows {
@@ -380,9 +380,11 @@ __device__ __forceinline__ float upper_f(Real t) {
 }
 
 // `stk`: this lane's column of the LDS node stack.
-// Walks the children-in-parent tree (RtTNode): one 64-byte node read tests
-// both children; the nearer hit child is taken, the farther pushed (with its
-// entry distance when kStackTnear, culled on pop against the best hit).
+// Walks the 4-wide tree (RtT4Node) from S.t4root after one slab test of the root box: a node
+// step (t4_step) reads one 128-byte node and tests its four children's boxes; the nearest hit
+// child is taken, the other hit children are pushed farthest first. Stack entries hold a node
+// reference only: a popped subtree is culled one level later by its children's slab tests
+// against the best hit so far. The result is the (t, slot) minimum over the leaves reached.
 //
 // Lanes of a wave reach leaves at different steps. Node steps and leaf tests run as two
 // separate loops: a lane that reaches a leaf
@@ -522,7 +524,7 @@ __device__ __forceinline__ int closest_hit_fast(const DevScene& S, const RayK<Re
         if (COUNT) cnt[CT_NODE] += 4;
         return t4_step<kStackStride>(S, ref, f, thi, stk, sp);
     };
-    int ref = S.troot;
+    int ref = S.t4root;
     int leaf = kTravDone;  // parked leaf
     while (ref != kTravDone || leaf != kTravDone) {
         while (ref >= 0) {
@@ -581,7 +583,7 @@ __device__ __forceinline__ void fast_walk_begin(const DevScene& S, V3 o, V3 d, F
     W.leaf = kTravDone;
     float tn0;
     if (COUNT) cnt[CT_NODE]++;
-    W.ref = slab(S.root_box, f, W.thi, tn0) ? S.troot : kTravDone;
+    W.ref = slab(S.root_box, f, W.thi, tn0) ? S.t4root : kTravDone;
 }
 
 // Called by the whole wave with uniform control flow; lanes with `walking`

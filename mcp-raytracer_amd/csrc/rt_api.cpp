@@ -167,9 +167,9 @@ int rt_camera_create(const char* scene_json, const char* render_options_json, rt
             if (env_flag("RT_AMD_LAUNCH_LOG", false)) {
                 const SceneBuild& b = cam->build;
                 std::fprintf(stderr,
-                             "[rt scene] prims %zu t4nodes %zu (%zu B) tnodes %zu tprims %zu B tsph %zu B prims %zu B "
+                             "[rt scene] prims %zu t4nodes %zu (%zu B) tprims %zu B tsph %zu B prims %zu B "
                              "mats %zu B lights %zu B nodes %zu stack_depth %d\n",
-                             b.prims.size(), b.t4nodes.size(), b.t4nodes.size() * sizeof(b.t4nodes[0]), b.tnodes.size(),
+                             b.prims.size(), b.t4nodes.size(), b.t4nodes.size() * sizeof(b.t4nodes[0]),
                              b.tprims.size() * 4, b.tsph.size() * 16, b.prims.size() * sizeof(RtPrim),
                              b.mats.size() * sizeof(RtMat), b.lights.size() * sizeof(RtLight), b.nodes.size(),
                              b.cam.stack_depth);
@@ -212,7 +212,7 @@ int rt_camera_get_info(const rt_camera* cam, rt_camera_info* info) {
     info->mode = C.mode;
     info->adaptive = C.adaptive;
     info->precision = cam->precision;
-    // effective traversal: fast/brute only where provably exact (scene.cpp prims_inside_boxes)
+    // effective traversal: fast/brute only where provably exact (scene_tree.cpp prims_inside_boxes)
     info->traversal = cam->effective_traversal(cam->traversal);
     info->seed = C.seed;
     info->samples = C.samples;

@@ -44,7 +44,7 @@ std::vector<RtOnb> planar_onbs(const std::vector<RtPrim>& prims, int32_t* n_onb)
     return t;
 }
 
-// The RtExact records (scene.hpp) of a brute-force scene's primitives (empty above
+// The RtExact records (scene_types.hpp) of a brute-force scene's primitives (empty above
 // kBruteMaxPrims: only closest_hit_brute_nf reads them)
 std::vector<RtExact> exact_records(const std::vector<RtPrim>& prims) {
     std::vector<RtExact> out;
@@ -78,7 +78,7 @@ std::vector<RtExact> exact_records(const std::vector<RtPrim>& prims) {
     return out;
 }
 
-// The RtPre records (scene.hpp) of the brute-force pre-filter pass, from the RtPrim fields:
+// The RtPre records (scene_types.hpp) of the brute-force pre-filter pass, from the RtPrim fields:
 // spheres in pairs, axis-aligned quads in pairs of one axis code, the rest (an odd one out,
 // planar quads, planes) one per record. The pass sets each primitive's candidate bit and
 // bound by its slot, so the records' order is free; pairs come first. Sets *n_rec.

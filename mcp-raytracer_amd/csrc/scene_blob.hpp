@@ -21,8 +21,8 @@ constexpr int kBlobBruteMaxPrims = 16;
 struct SceneBlob {
     std::vector<char> bytes;  // (a device context drops them after the upload)
     size_t size = 0;          // their count
-    int32_t lds_words = 0;    // [tnodes][tprims][tsph][prims] prefix, 16-byte words
-    int32_t lds_words2 = 0;   // the same + [mats][lights]
+    int32_t lds_words = 0;    // [t4nodes][tprims][tsph][prims][xrec] prefix, 16-byte words
+    int32_t lds_words2 = 0;   // the same + [mats][lights][onbs]
     int32_t off_prims = 0, off_mats = 0, off_lights = 0, off_nodes = 0, off_tprims = 0, off_tsph = 0, off_onbs = 0;
     int32_t off_tsph2 = -1;  // leaf-order sphere records with the fp64 radius (RtLeafSph), or -1
     int32_t off_pre = 0, n_pre = 0, off_xrec = 0;

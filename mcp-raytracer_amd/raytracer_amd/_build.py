@@ -93,11 +93,13 @@ _UNITS = [
     ("multi_gpu.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     # plain C++ (no device, no HIP runtime)
     ("scene.cpp", ["-ffp-contract=off"], False),
+    ("scene_gen.cpp", ["-ffp-contract=off"], False),
+    ("scene_tree.cpp", ["-ffp-contract=off"], False),
     ("scene_blob.cpp", ["-ffp-contract=off"], False),
     ("prog_blob.cpp", ["-ffp-contract=off"], False),
     ("image.cpp", [], False),
 ]
-_HEADERS = ["json.hpp", "rt_math.hpp", "scene.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
+_HEADERS = ["json.hpp", "rt_math.hpp", "scene_types.hpp", "scene.hpp", "scene_js.hpp", "scene_tree.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
             "pt_brute.hpp", "pt_shade.hpp", "pt_pixel.hpp", "pt_kernels.hpp", "pt_pool.hpp", "pt_dispatch.hpp",
             "launch.hpp", "progressive.hpp", "denoise.hpp",
             "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
