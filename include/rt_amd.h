@@ -612,9 +612,10 @@ int rt_camera_progressive_denoise_variance(rt_camera* cam, const rt_denoise_var_
  * guide_ms covers whichever pass ran. RT_ERR_INVALID, decided before any device call: an unknown
  * mode, max_bounces outside 1..64, a negative or non-finite max_fuzz.
  * Limits: one deterministic branch per interface (no Schlick split), fuzzy metals above max_fuzz
- * are terminal, a defocused camera's blur is not in the guides, and rt_reproject and the view
- * history still stop at specular surfaces (rt_reproject_specular and its camera calls, below,
- * follow the chains on request). Not in the N-API addon or the multi-GPU render. */
+ * are terminal, a defocused camera's blur is not in the guides, and rt_reproject and
+ * rt_camera_progressive_accumulate still stop at specular surfaces (rt_reproject_specular and
+ * rt_camera_progressive_accumulate_specular with their sibling calls, below, follow the chains on
+ * request). Not in the N-API addon or the multi-GPU render. */
 enum { RT_GUIDES_FIRST_HIT = 0, RT_GUIDES_SPECULAR = 1 };
 typedef struct { int32_t mode; int32_t max_bounces; float max_fuzz; } rt_guide_options;
 void rt_guide_options_default(rt_guide_options* options);
@@ -804,7 +805,8 @@ int rt_camera_progressive_reproject_specular(rt_camera* cam, rt_camera* prev_cam
  * that share a seed have correlated noise, and a static camera with the same seed re-renders the
  * very same samples - nothing is gained and the carried variance is wrong.
  *
- * Limits as the reprojection block (lambert and light surfaces only, unchanged lighting).
+ * Limits as the reprojection block (lambert and light surfaces only, unchanged lighting; what a
+ * mirror or glass shows gets a history through rt_camera_progressive_accumulate_specular, below).
  * max_history (default 256) bounds the weight of the past; it is a design choice, not tuned.
  *
  * RT_ERR_INVALID, decided before any device call: negative or non-finite options or
@@ -854,6 +856,92 @@ int rt_temporal_accumulate(int32_t width, int32_t height, const rt_region* regio
  * without one), and the whole span up to the unpacked outputs and the commit's guide copy (host
  * copies excluded). Waits for the events. */
 int rt_history_times(rt_history* h, float* guide_ms, float* gather_ms, float* filter_ms, float* total_ms);
+
+/* ---- Accumulation across views through mirrors and glass (specular chains) ----------------------
+ * Opt-in like the blocks above: no other call changes, and a history that never sees a call of this
+ * block holds the device bytes it held before. The view history above stops at every specular
+ * surface (reusable[o] == 0: weight 0, the length restarts at the fresh count on every view). This
+ * block carries it through the chains of the specular-reprojection block: the history keeps, beside
+ * the first-hit planes of the view it was committed from, that view's chain planes, chain words and
+ * the {max_bounces, max_fuzz} they were walked with. tests/specular_temporal_ref.py is the normative
+ * definition; in words, with the rules of the two blocks it combines (fp32, no fused multiply-add,
+ * their dot, projection, tap order and multiply-then-add sums):
+ *
+ * Per pixel of the new region: the first-hit guides n1, P1, D1, o1; the guides through the chain
+ * n, P, Ds, o and the chain word ch of ONE rt_guide_options, k = ch & 0xff, e = (ch >> 8) & 0xff;
+ * the new view's centre cn; the fresh colour c, its sample count m and variance v, sanitised as the
+ * accumulation block does. The history holds c', L', V' and the planes above for its view.
+ *   k == 0  the accumulation block's steps 1-3 verbatim on n1, P1, D1, o1 against the history's
+ *           first-hit planes; kind = 1 where weight > 0.
+ *   k >= 1  no history unless the history holds chain planes walked with bit-equal guide options
+ *           and the specular-reprojection block's conditions hold: e == 1, 0 <= o < n_objects and
+ *           reusable[o], 0 <= o1 < n_objects and through[o1], P, P1 and Ds finite, D1 finite and
+ *           > 0. Then r = Ds / D1, X = cn + (P1 - cn) r, and X is projected in place of P. A tap
+ *           counts iff it passes that block's chain tap test (equal chain word, first-hit object
+ *           == o1, chain object == o, n.n' >= normal_min, |n.(P' - P)| <= sigma_plane Ds,
+ *           q.q <= (pp2 Ds) Ds) with the accumulation block's colour and length conditions (c'
+ *           finite, L' finite and > 0) in place of the finite flag. ws, acc, av, al, the min_weight
+ *           cut, h, Vh, Lh, N = min(Lh, max_history) and the three blend cases are the accumulation
+ *           block's steps 2-3 unchanged; kind = 2 where weight > 0.
+ *   filter_levels > 0: step 4 with the CHAIN guides of the new view as the filter's guides (what
+ *           rt_camera_set_denoise_guides selects for the filters), so what a mirror shows is
+ *           edge-stopped by the surface it shows. length_out, weight_out and kind_out are never
+ *           filtered; the history keeps the unfiltered values.
+ *   Commit: as step 5, plus the new view's chain planes, chain words and guide options.
+ * Plain and specular calls mix freely on one history. rt_camera_progressive_accumulate is bit for
+ * bit what it was and commits a view without chain planes. A specular call uses the history's chain
+ * planes only if the last committed view holds them AND they were walked with bit-equal
+ * max_bounces and max_fuzz; otherwise every k >= 1 pixel has weight 0 and the call commits its own.
+ *
+ * THE CALLER MUST VARY THE SEED PER VIEW, as above. Limits as the specular-reprojection block: a
+ * curved mirror's image does not lie at the summed length, so it gets little or no history; glass
+ * is approximate (the Schlick split varies with the angle); grazing reflections are under-covered
+ * by the isotropic point check; chains that leave the scene or reach max_bounces get none; the
+ * lighting must be unchanged. Not in the N-API addon and not in the multi-GPU render.
+ *
+ * RT_ERR_INVALID, decided before any device call: everything the two blocks refuse - negative or
+ * non-finite temporal options, filter_levels outside 0..8, guide options
+ * rt_camera_render_guides_ex would refuse, mode RT_GUIDES_FIRST_HIT, a negative or non-finite
+ * point_pixels, a through mask outside 0..15, no open session, mode bounces / samples,
+ * samples_done < 2, a history of another scene or device, a missing pointer or an empty region of
+ * the explicit entry - and some but not all of its prev_chain* arguments NULL. */
+typedef struct { rt_temporal_options base; float point_pixels; int32_t through; } rt_specular_temporal_options;   /* NULL or a zero field = default (base's, 4, 15) */
+/* {{0.9, 0.01, 0.25, 256, 0, 2.0}, 4, 15}. Host only. */
+void rt_specular_temporal_options_default(rt_specular_temporal_options* options);
+/* held = 1 iff the last committed view holds chain planes; out then receives the options they were
+ * walked with (mode RT_GUIDES_SPECULAR), else {RT_GUIDES_SPECULAR, 0, 0}. Host only. */
+int rt_history_chain_guides(const rt_history* h, rt_guide_options* out, int32_t* held);
+/* rt_camera_progressive_accumulate through the chains: the session's kept first-hit guides and its
+ * kept chain guides with their chain plane serve (those rt_camera_progressive_reproject_specular
+ * and the filters keep, walked again when the options change); guide_options NULL =
+ * {RT_GUIDES_SPECULAR, 8, 0}; the through table is the camera's for options->through and
+ * guide_options->max_fuzz, kept by the history and rebuilt when either changes. kind_out: HOST
+ * width*height uint8 (0 none, 1 first hit, 2 chain), only the region written. The session's state,
+ * frame, stats and the bytes of rt_camera_progressive_save are never touched. rt_history_times
+ * covers the call; its guide_ms includes the chain walk. */
+int rt_camera_progressive_accumulate_specular(rt_camera* cam, rt_history* h, const rt_guide_options* guide_options,
+                                              const rt_specular_temporal_options* options, int32_t commit, uint8_t* rgb,
+                                              float* radiance, float* variance_out, float* length_out, float* weight_out,
+                                              uint8_t* kind_out);
+/* Explicit HOST buffers, no camera and no history object (the calling thread's current device), as
+ * rt_temporal_accumulate, plus the new `view`, both views' chain guides and chain words (walked
+ * with one rt_guide_options), `through` and kind_out. prev_chain_normal .. prev_chain all NULL: the
+ * history holds no chain planes; some but not all of them NULL: RT_ERR_INVALID. */
+int rt_temporal_accumulate_specular(int32_t width, int32_t height, const rt_region* region, const float* normal,
+                                    const float* position, const float* distance, const int32_t* object,
+                                    const float* chain_normal, const float* chain_position, const float* chain_distance,
+                                    const int32_t* chain_object, const int32_t* chain, const rt_view* view,
+                                    const float* radiance, const int32_t* px_samples, int32_t samples,
+                                    const float* variance, const rt_view* prev_view, const rt_region* prev_region,
+                                    const float* prev_normal, const float* prev_position, const float* prev_distance,
+                                    const int32_t* prev_object, const float* prev_chain_normal,
+                                    const float* prev_chain_position, const float* prev_chain_distance,
+                                    const int32_t* prev_chain_object, const int32_t* prev_chain,
+                                    const float* prev_radiance, const float* prev_variance, const float* prev_length,
+                                    const uint8_t* reusable, const uint8_t* through, int32_t n_objects,
+                                    const rt_specular_temporal_options* options, float* radiance_out,
+                                    float* variance_out, float* length_out, float* weight_out, uint8_t* rgb_out,
+                                    uint8_t* kind_out);
 
 /* ---- Focused steps: the next samples go to the noisiest pixels ---------------------------------
  * No reference counterpart (the reference gives every pixel the same loop). Opt-in: a session

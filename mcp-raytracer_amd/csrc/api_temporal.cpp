@@ -8,13 +8,7 @@
 
 using namespace rt;
 
-// rt_temporal_options resolved: a zero field = the default; levels 0 = no filter.
-struct TpOpts : GatherOpts {
-    float max_history;
-    int32_t levels;
-    float sigma_variance;
-};
-static TpOpts tp_resolve(const rt_temporal_options* o, const std::string& who) {
+TpOpts rt::tp_resolve(const rt_temporal_options* o, const std::string& who) {
     const rt_temporal_options z = o ? *o : rt_temporal_options{0.0f, 0.0f, 0.0f, 0.0f, 0, 0.0f};
     TpOpts r{gather_resolve(z.normal_min, z.sigma_plane, z.min_weight, who), 0.0f, z.filter_levels, 0.0f};
     r.max_history = resolve_field(z.max_history, 256.0f, who, "max_history");
@@ -26,7 +20,7 @@ static TpOpts tp_resolve(const rt_temporal_options* o, const std::string& who) {
 }
 
 // The hash a history keeps of its scene: the arrays the reprojection's same-scene check compares.
-static uint64_t tp_scene_hash(const SceneBuild& b) {
+uint64_t rt::tp_scene_hash(const SceneBuild& b) {
     uint64_t f = fnv1a(b.nodes.data(), b.nodes.size() * sizeof(RtNode));
     f = fnv1a(b.prims.data(), b.prims.size() * sizeof(RtPrim), f);
     f = fnv1a(b.mats.data(), b.mats.size() * sizeof(RtMat), f);
@@ -49,6 +43,13 @@ static void tp_run(DnBufs& b, const TpNew& nw, const rt_region& r, const TpHisto
     hip_check(launch_temporal(a, nw.gn, nw.gp, hist, d_reusable, nw.fresh, nw.pxs, nw.var, TpOut{out_col, out_var, b.dist()},
                               stream),
               "temporal_kernel");
+    tp_finish(b, nw.gn, nw.gp, r, o, out_col, out_var, want_rad, want_u8, want_var, want_len, stream, ev);
+}
+
+void rt::tp_finish(DnBufs& b, const float4* fgn, const float4* fgp, const rt_region& r, const TpOpts& o, float4* out_col,
+                   float* out_var, bool want_rad, bool want_u8, bool want_var, bool want_len, hipStream_t stream,
+                   hipEvent_t* ev) {
+    const int n = r.width * r.height;
     if (ev) hip_check(hipEventRecord(ev[2], stream), "hipEventRecord");
     const bool filter = o.levels > 0 && (want_rad || want_u8 || want_var);
     if (filter || want_var) {
@@ -58,7 +59,7 @@ static void tp_run(DnBufs& b, const TpNew& nw, const rt_region& r, const TpHisto
     }
     if (filter) {
         hip_check(launch_denoise_unpack(out_col, n, b.rad(), nullptr, nullptr, stream), "denoise_unpack_kernel");
-        dn_filter(b, nw.gn, nw.gp, b.rad(), r.width, 0, 0, r.width, r.height,
+        dn_filter(b, fgn, fgp, b.rad(), r.width, 0, 0, r.width, r.height,
                   DnOpts{true, o.levels, o.sigma_variance, o.sigma_plane}, want_rad, want_u8, want_var, stream, nullptr);
     }
     if (ev) hip_check(hipEventRecord(ev[3], stream), "hipEventRecord");
@@ -68,9 +69,8 @@ static void tp_run(DnBufs& b, const TpNew& nw, const rt_region& r, const TpHisto
     if (want_len) hip_check(launch_denoise_unpack(out_col, n, nullptr, nullptr, b.nrm(), stream), "denoise_unpack_kernel");
 }
 
-// A call's outputs into the caller's arrays, then its one host sync.
-static void tp_outputs(const DnBufs& b, const RegionIo& io, float* radiance, uint8_t* rgb, float* variance, float* length,
-                       float* weight) {
+void rt::tp_outputs(const DnBufs& b, const RegionIo& io, float* radiance, uint8_t* rgb, float* variance, float* length,
+                    float* weight) {
     io.down(radiance, b.rad(), 3 * sizeof(float));
     io.down(rgb, b.u8, 3);
     io.down(variance, b.var, sizeof(float));
@@ -178,6 +178,7 @@ int rt_camera_progressive_accumulate(rt_camera* cam, rt_history* h, const rt_tem
             // the session may be gone before the next view: the history keeps the guides itself
             hip_check(hipMemcpyAsync(back.gn, P.d_gn, n * sizeof(float4), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync");
             hip_check(hipMemcpyAsync(back.gp, P.d_gp, n * sizeof(float4), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync");
+            back.has_chain = false;  // (a specular commit may have left chain planes of an older view)
         }
         hip_check(hipEventRecord(h->ev[4], stream), "hipEventRecord");
         h->timed = true;

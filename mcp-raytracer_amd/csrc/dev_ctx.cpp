@@ -627,7 +627,9 @@ void rt_history::release() {
         side[0] = Side{};
         side[1] = Side{};
         d_reusable.reset();
+        d_through.reset();
     }
+    through_mask = -1;
     views = 0, device = -1, alloc_device = -1, front = 0, n_objects = 0;
     width = height = 0;
     region = rt_region{};

@@ -383,10 +383,29 @@ struct rt_history {
             for (rt::DevBuf<float4>* p : {&col, &gn, &gp}) p->ensure(n, "hipMalloc(history)");
             var.ensure(n, "hipMalloc(history)");
         }
-        size_t bytes() const { return (col.cap + gn.cap + gp.cap) * sizeof(float4) + var.cap * sizeof(float); }
+        // the chain planes of that view (temporal_spec.hpp), allocated by the first specular commit:
+        // its guides through the chain and its chain words, held when has_chain, walked with chain_go
+        rt::DevBuf<float4> sgn, sgp;
+        rt::DevBuf<int32_t> chain;
+        bool has_chain = false;
+        rt_guide_options chain_go{};
+        void ensure_chain(size_t n) {
+            sgn.ensure(n, "hipMalloc(history)");
+            sgp.ensure(n, "hipMalloc(history)");
+            chain.ensure(n, "hipMalloc(history)");
+        }
+        size_t bytes() const {
+            return (col.cap + gn.cap + gp.cap + sgn.cap + sgp.cap) * sizeof(float4) + var.cap * sizeof(float) +
+                   chain.cap * sizeof(int32_t);
+        }
     } side[2];
     int front = 0;
     rt::DevBuf<uint8_t> d_reusable;
+    // object index -> 1: a chain may start on it, for the mask and max_fuzz it was built from
+    // (the specular calls; rebuilt when either changes)
+    rt::DevBuf<uint8_t> d_through;
+    int32_t through_mask = -1;
+    float through_fuzz = 0.0f;
     int32_t n_objects = 0;
     int32_t views = 0, device = -1;
     int32_t width = 0, height = 0;

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "api_call.hpp"
 
@@ -130,5 +131,34 @@ Args gather_args(const RpView& view, const rt_region& r, const rt_region& pr, in
     a.m = nw.m;
     return a;
 }
+
+// ---- what the accumulation's two ABI units share (api_temporal.cpp) --------------------------------
+// rt_temporal_options resolved: a zero field = the default; levels 0 = no filter.
+struct TpOpts : GatherOpts {
+    float max_history;
+    int32_t levels;
+    float sigma_variance;
+};
+TpOpts tp_resolve(const rt_temporal_options* o, const std::string& who);
+// The hash a history keeps of its scene: the arrays the reprojection's same-scene check compares.
+uint64_t tp_scene_hash(const SceneBuild& b);
+// What follows the gather kernel of a call, which wrote out_col / out_var (weight -> b.dist()): the
+// caller's outputs - the optional variance-guided filter of out / Vout on the guides fgn / fgp,
+// else out itself - into b.rad() / b.u8 / b.var, and the length into b.nrm(). ev (or null): events
+// 2 and 3, recorded after the gather and after the filter. Queued.
+void tp_finish(DnBufs& b, const float4* fgn, const float4* fgp, const rt_region& r, const TpOpts& o, float4* out_col,
+               float* out_var, bool want_rad, bool want_u8, bool want_var, bool want_len, hipStream_t stream,
+               hipEvent_t* ev);
+// A call's outputs into the caller's arrays, then its one host sync.
+void tp_outputs(const DnBufs& b, const RegionIo& io, float* radiance, uint8_t* rgb, float* variance, float* length,
+                float* weight);
+
+// ---- what the two specular ABI units share (reproject_spec_api.cpp) --------------------------------
+// The guide options of a call: NULL = the specular walk's defaults; first-hit guides have no chains.
+rt_guide_options rs_guide_options(const rt_guide_options* go, const std::string& who);
+// through[o] for the mask and max_fuzz, as rt_camera_through_objects returns it.
+std::vector<uint8_t> through_objects(const CamHost& h, int32_t mask, float max_fuzz);
+// (pp * pp) * (du.du / a.a) of a view: each product, sum and the division rounded once.
+float rs_pp2(const RpView& v, float pp);
 
 }  // namespace rt

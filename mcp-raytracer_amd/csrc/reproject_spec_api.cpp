@@ -26,7 +26,7 @@ static RsOpts rs_resolve(const rt_specular_reproject_options* o, const std::stri
 }
 
 // The guide options of a call: NULL = the specular walk's defaults; first-hit guides have no chains.
-static rt_guide_options rs_guide_options(const rt_guide_options* go, const std::string& who) {
+rt_guide_options rt::rs_guide_options(const rt_guide_options* go, const std::string& who) {
     const rt_guide_options dflt{RT_GUIDES_SPECULAR, 8, 0.0f};
     const rt_guide_options g = guide_options(go ? go : &dflt, who);
     if (g.mode != RT_GUIDES_SPECULAR) throw std::invalid_argument(who + ": guide_options must have mode RT_GUIDES_SPECULAR");
@@ -35,7 +35,7 @@ static rt_guide_options rs_guide_options(const rt_guide_options* go, const std::
 
 // through[o] = 1 iff SceneData.objects[o]'s material (resolved to a table index by the build) is
 // in `mask`: 1 a metal of fuzz <= max_fuzz (the walk's own comparison), 2 glass, 4 mixed, 8 layered.
-static std::vector<uint8_t> through_objects(const CamHost& h, int32_t mask, float max_fuzz) {
+std::vector<uint8_t> rt::through_objects(const CamHost& h, int32_t mask, float max_fuzz) {
     const SceneBuild& b = h.build;
     std::vector<uint8_t> t((size_t)std::max(b.cam.n_prims, 0), 0);
     for (size_t s = 0; s < b.prims.size() && s < b.prim_object.size(); ++s) {
@@ -74,7 +74,7 @@ static const uint8_t* ensure_through(DevCtx& c, int32_t mask, float max_fuzz) {
 
 // (pp * pp) * (du.du / a.a): each product, sum and the division rounded once (this unit is
 // compiled without contraction).
-static float rs_pp2(const RpView& v, float pp) {
+float rt::rs_pp2(const RpView& v, float pp) {
     auto dot = [](const float* a, const float* b) {
         const float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
         const float xy = x + y;

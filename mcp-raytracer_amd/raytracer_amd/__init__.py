@@ -22,11 +22,13 @@ with `guides="specular"` (reproject_specular, Camera.through_objects) what a mir
 finds its history too. A History follows a camera
 along a path on the device: ProgressiveRender.accumulated blends each view's frame onto it by
 per-pixel history lengths and carries a variance the variance-guided filter consumes
-(temporal_accumulate: the same with explicit buffers). Vary `seed` per view.
+(temporal_accumulate: the same with explicit buffers); with `guides="specular"`
+(temporal_accumulate_specular, History.chain_guides) the history follows mirrors and glass to the
+surface they show. Vary `seed` per view.
 """
 from ._lib import RtError, build_id, device_count, progressive_blob_info, progressive_blob_variance
 from .camera import (Camera, History, ProgressiveRender, RenderStats, denoise, reproject, reproject_specular,
-                     rng_stream, temporal_accumulate)
+                     rng_stream, temporal_accumulate, temporal_accumulate_specular)
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
                      generate_scene_data, generateScene, generateSceneData)
@@ -34,7 +36,7 @@ from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, g
 __all__ = [
     "Camera", "ProgressiveRender", "RenderStats", "RtError", "build_id", "device_count", "rng_stream",
     "progressive_blob_info", "progressive_blob_variance", "denoise", "reproject", "reproject_specular", "History",
-    "temporal_accumulate",
+    "temporal_accumulate", "temporal_accumulate_specular",
     "generate_scene_data", "create_camera_from_scene_data", "generate_scene",
     "generate_image_buffer", "divide_into_regions",
     "generateSceneData", "createCameraFromSceneData", "generateScene", "generateImageBuffer",

@@ -66,6 +66,9 @@ _UNITS = [
     # the accumulation across views: the same rule - the output equals tests/temporal_ref.py in
     # every bit
     ("temporal.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the accumulation across views through specular chains: temporal.hip's flags and rule - the
+    # output equals tests/specular_temporal_ref.py in every bit
+    ("temporal_spec.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the focused steps' selection: its score is progressive.hpp's prog_variance, evaluated as
     # progressive.hip evaluates it; the rest is integer work - the selected set equals
     # tests/focus_ref.py exactly
@@ -87,6 +90,8 @@ _UNITS = [
     # pp2 is a host computation that must not be contracted
     ("reproject_spec_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("api_temporal.cpp", ["-ffp-contract=off", "-x", "hip"], True),
+    # the ABI unit of the accumulation through specular chains, with the api_* units' flags
+    ("temporal_spec_api.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("api_focus.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("dev_ctx.cpp", ["-ffp-contract=off", "-x", "hip"], True),
     ("launch_plan.cpp", ["-ffp-contract=off", "-x", "hip"], True),
@@ -102,7 +107,7 @@ _UNITS = [
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene_types.hpp", "scene.hpp", "scene_js.hpp", "scene_tree.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
             "pt_brute.hpp", "pt_shade.hpp", "pt_pixel.hpp", "pt_kernels.hpp", "pt_pool.hpp", "pt_dispatch.hpp",
             "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "temporal_spec.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp", "api_call.hpp", "pass_host.hpp"]
 _LIBS = ["-lz"]
 

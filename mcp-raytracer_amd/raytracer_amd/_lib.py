@@ -127,6 +127,10 @@ class RtTemporalOptions(C.Structure):
                 ("max_history", C.c_float), ("filter_levels", C.c_int32), ("sigma_variance", C.c_float)]
 
 
+class RtSpecularTemporalOptions(C.Structure):
+    _fields_ = [("base", RtTemporalOptions), ("point_pixels", C.c_float), ("through", C.c_int32)]
+
+
 class RtHistoryInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("region", RtRegion), ("views", C.c_int32),
                 ("device", C.c_int32), ("scene_hash", C.c_uint64), ("bytes", C.c_uint64), ("view", RtView)]
@@ -313,6 +317,16 @@ _SIGS = {
                                          C.c_void_p]),
     "rt_history_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float)]),
+    "rt_specular_temporal_options_default": (None, [C.POINTER(RtSpecularTemporalOptions)]),
+    "rt_history_chain_guides": (C.c_int, [C.c_void_p, C.POINTER(RtGuideOptions), C.POINTER(C.c_int32)]),
+    "rt_camera_progressive_accumulate_specular": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtGuideOptions),
+                                                            C.POINTER(RtSpecularTemporalOptions), C.c_int32,
+                                                            *[C.c_void_p] * 6]),
+    "rt_temporal_accumulate_specular": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), *[C.c_void_p] * 9,
+                                                  C.POINTER(RtView), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                  C.POINTER(RtView), C.POINTER(RtRegion), *[C.c_void_p] * 9,
+                                                  *[C.c_void_p] * 3, C.c_void_p, C.c_void_p, C.c_int32,
+                                                  C.POINTER(RtSpecularTemporalOptions), *[C.c_void_p] * 6]),
     "rt_focus_options_default": (None, [C.POINTER(RtFocusOptions)]),
     "rt_camera_progressive_focus": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(RtFocusOptions), C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

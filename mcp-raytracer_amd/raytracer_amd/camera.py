@@ -400,6 +400,78 @@ def temporal_accumulate(prev_radiance, prev_variance, prev_length, prev_view, pr
     return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
 
 
+def _specular_temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance,
+                               point_pixels, through):
+    """rt_specular_temporal_options (a zero field = the default; the library validates the rest)."""
+    return _lib.RtSpecularTemporalOptions(
+        _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance),
+        float(point_pixels), int(through))
+
+
+def temporal_accumulate_specular(prev_radiance, prev_variance, prev_length, prev_view, prev_first, prev_chain, view, first,
+                                 chain, reusable, through, *, radiance, variance, px_samples=None, samples=None,
+                                 region=None, prev_region=None, rgb=None, out=None, variance_out=None, length_out=None,
+                                 weight_out=None, kind=None, filter_levels=0, sigma_variance=2.0, normal_min=0.9,
+                                 sigma_plane=0.01, min_weight=0.25, max_history=256.0, point_pixels=4.0):
+    """rt_temporal_accumulate_specular: temporal_accumulate() through specular chains, explicit
+    buffers, no camera and no History. first / prev_first: the new and the previous view's first-hit
+    guides as Camera.render_guides() returns them; chain / prev_chain: their guides through the
+    chain, render_guides(through_specular=True) of one max_bounces / max_fuzz (with "chain");
+    prev_chain=None: the history holds no chain planes (every pixel behind a chain starts over);
+    view: the new camera's Camera.view(); reusable / through: uint8 per object, as
+    Camera.reusable_objects() and Camera.through_objects(). A pixel whose chain has length 0 is
+    temporal_accumulate()'s; a pixel that shows a lambert or light surface through a chain finds its
+    history - colour, length and variance - at the chain's virtual point. `kind` (optional uint8
+    (H, W)) receives 0 no history, 1 first hit, 2 chain. filter_levels > 0 filters with the chain
+    guides. Everything else as temporal_accumulate(). Equals tests/specular_temporal_ref.py in every
+    bit. Views must be rendered with different seeds."""
+    import numpy as np
+    obj = np.asarray(first["object"])
+    if obj.ndim != 2:
+        raise ValueError("object must have shape (H, W)")
+    H, W = obj.shape
+    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
+
+    def planes(g, h, w, with_chain):
+        a = [_f32_frame(g["normal"], (h, w, 3), "normal"), _f32_frame(g["position"], (h, w, 3), "position"),
+             _f32_frame(g["distance"], (h, w), "distance"), _f32_frame(g["object"], (h, w), "object")]
+        if with_chain:
+            a.append(_f32_frame(g["chain"], (h, w), "object"))
+        return a
+    g = planes(first, H, W, False) + planes(chain, H, W, True)
+    pg = planes(prev_first, Hp, Wp, False)
+    pcg = planes(prev_chain, Hp, Wp, True) if prev_chain is not None else None
+    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
+    pvar = _f32_frame(prev_variance, (Hp, Wp), "prev_variance")
+    plen = _f32_frame(prev_length, (Hp, Wp), "prev_length")
+    rad = _f32_frame(radiance, (H, W, 3), "radiance")
+    var = _f32_frame(variance, (H, W), "variance")
+    pxs = None if px_samples is None else np.ascontiguousarray(px_samples, dtype=np.int32)
+    if pxs is not None and pxs.size != H * W:
+        raise ValueError(f"px_samples must hold {H}x{W} values, not {pxs.size}")
+    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
+    thr = np.ascontiguousarray(through, dtype=np.uint8).ravel()
+    if thr.size != reus.size:
+        raise ValueError("reusable and through must hold one entry per object")
+    res = _denoise_out(rad, out)
+    uptr, _keep = _host_ptr(rgb, H * W * 3, "rgb")
+    reg = None if region is None else _region(region)
+    preg = None if prev_region is None else _region(prev_region)
+    opts = _specular_temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance,
+                                      point_pixels, 0)
+    v, pv = _c_view(view), _c_view(prev_view)
+    _lib.check(_lib.load().rt_temporal_accumulate_specular(
+        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], C.byref(v), rad.ctypes.data,
+        None if pxs is None else pxs.ctypes.data, 0 if samples is None else int(samples), var.ctypes.data, C.byref(pv),
+        C.byref(preg) if preg is not None else None, *[a.ctypes.data for a in pg],
+        *([a.ctypes.data for a in pcg] if pcg is not None else [None] * 5), prad.ctypes.data, pvar.ctypes.data,
+        plen.ctypes.data, reus.ctypes.data if reus.size else None, thr.ctypes.data if thr.size else None, int(reus.size),
+        C.byref(opts), res.ctypes.data, _out_array(variance_out, np.float32, (H, W), "variance_out"),
+        _out_array(length_out, np.float32, (H, W), "length_out"),
+        _out_array(weight_out, np.float32, (H, W), "weight_out"), uptr, _kind_out(kind, (H, W))))
+    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+
+
 class History:
     """A view history (rt_history_*): per pixel the accumulated radiance, the effective number of
     samples behind it and the variance of the accumulated mean's illuminance, kept on the device
@@ -435,6 +507,14 @@ class History:
     @property
     def views(self) -> int:
         return self.info["views"]
+
+    @property
+    def chain_guides(self) -> Optional[dict]:
+        """rt_history_chain_guides: None, or {"max_bounces", "max_fuzz"} of the chain planes the last
+        committed view holds (a commit of ProgressiveRender.accumulated(guides=...))."""
+        go, held = _lib.RtGuideOptions(), C.c_int32(0)
+        _lib.check(self._lib.rt_history_chain_guides(self._handle(), C.byref(go), C.byref(held)))
+        return {"max_bounces": int(go.max_bounces), "max_fuzz": float(go.max_fuzz)} if held.value else None
 
     def read(self) -> dict:
         """rt_history_read: {"radiance": float32 (H, W, 3), "variance", "length": float32 (H, W)} in
@@ -1090,7 +1170,8 @@ class ProgressiveRender:
 
     def accumulated(self, history: History, rgb=None, radiance=None, *, commit=True, variance_out=None,
                     length_out=None, weight_out=None, filter_levels=0, sigma_variance=2.0, normal_min=0.9,
-                    sigma_plane=0.01, min_weight=0.25, max_history=256.0):
+                    sigma_plane=0.01, min_weight=0.25, max_history=256.0, guides=None, point_pixels=4.0, through=15,
+                    kind=None):
         """The session's frame as it stands after the last step, accumulated onto `history`
         (rt_camera_progressive_accumulate): every pixel's history - gathered from the history's
         view as reprojected() does - is blended by its own length N = min(length, max_history)
@@ -1103,7 +1184,14 @@ class ProgressiveRender:
         `length_out`, `weight_out` (float32 (H, W)) are optional caller-owned full-frame buffers;
         only the region is written. Returns the radiance as a (H, W, 3) array. Needs
         samples_done >= 2, and every view rendered with its own `seed`: views that share a seed
-        have correlated noise and the carried variance is then wrong."""
+        have correlated noise and the carried variance is then wrong.
+        `guides` ("specular", or a dict of max_bounces / max_fuzz) carries the history through
+        mirrors and glass (rt_camera_progressive_accumulate_specular): a pixel behind a specular
+        chain finds its history at the chain's virtual point, on the chain planes the history keeps
+        of its view (History.chain_guides) - if a call with the same `guides` committed them; the
+        filter then uses the chain guides. `point_pixels`, `through` and `kind` (uint8 (H, W): 0 no
+        history, 1 first hit, 2 chain) as in reprojected(); they need guides=. Plain and specular
+        calls mix freely on one history; the session's state and checkpoint bytes are not touched."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
         import numpy as np
@@ -1113,12 +1201,22 @@ class ProgressiveRender:
             radiance = np.zeros(shape, np.float32)
         ptr, _k0 = _host_ptr(rgb, cam.byte_length, "rgb")
         rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
-        opts = _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance)
-        _lib.check(cam._lib.rt_camera_progressive_accumulate(
-            cam._h, history._handle(), C.byref(opts), 1 if commit else 0, ptr, rptr,
-            _out_array(variance_out, np.float32, shape[:2], "variance_out"),
-            _out_array(length_out, np.float32, shape[:2], "length_out"),
-            _out_array(weight_out, np.float32, shape[:2], "weight_out")))
+        outs = (_out_array(variance_out, np.float32, shape[:2], "variance_out"),
+                _out_array(length_out, np.float32, shape[:2], "length_out"),
+                _out_array(weight_out, np.float32, shape[:2], "weight_out"))
+        if guides is None:
+            if kind is not None or point_pixels != 4.0 or through != 15:
+                raise ValueError("kind, point_pixels and through need guides=")
+            opts = _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance)
+            _lib.check(cam._lib.rt_camera_progressive_accumulate(
+                cam._h, history._handle(), C.byref(opts), 1 if commit else 0, ptr, rptr, *outs))
+        else:
+            go = _guide_options(guides)
+            opts = _specular_temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels,
+                                              sigma_variance, point_pixels, through)
+            _lib.check(cam._lib.rt_camera_progressive_accumulate_specular(
+                cam._h, history._handle(), C.byref(go), C.byref(opts), 1 if commit else 0, ptr, rptr, *outs,
+                _kind_out(kind, shape[:2])))
         if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
             return radiance.reshape(shape)
         return radiance
