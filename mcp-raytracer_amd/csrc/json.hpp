@@ -68,6 +68,7 @@ public:
 
 class Parser {
 public:
+    static constexpr int kMaxDepth = 1000;
     Parser(const char* s, size_t n) : p_(s), end_(s + n), begin_(s) {}
     Value parse_document() {
         Value v = parse_value();
@@ -80,6 +81,16 @@ private:
     const char* p_;
     const char* end_;
     const char* begin_;
+    int depth_ = 0;  // arrays and objects open around p_
+
+    // The parser recurses once per open array or object; hostile text must not spend the stack.
+    struct Nest {
+        Parser& p;
+        explicit Nest(Parser& q) : p(q) {
+            if (++p.depth_ > kMaxDepth) p.fail("nesting deeper than 1000");
+        }
+        ~Nest() { --p.depth_; }
+    };
 
     [[noreturn]] void fail(const char* what) {
         char buf[160];
@@ -186,6 +197,7 @@ private:
         return out;
     }
     Value parse_array() {
+        Nest nest(*this);
         ++p_;
         Value v = Value::array();
         skip_ws();
@@ -200,6 +212,7 @@ private:
         }
     }
     Value parse_object() {
+        Nest nest(*this);
         ++p_;
         Value v = Value::object();
         skip_ws();

@@ -168,7 +168,12 @@ LaunchPlan plan_launch(const CamHost& host, const SceneBlob& blob, int cus, int 
     const bool rounds = C.adaptive && count != 1 && env_flag("RT_AMD_ADAPT_ROUNDS", true);
     plan.rounds = rounds;
     // sequential-pixel kernel (pixelConverged needs each pixel's samples in one place)
-    plan.sequential = prog_len <= 0 && (C.n_samples <= 0 || !chunked || (C.adaptive && !rounds));
+    // aTolerance NaN is not adaptive sampling (NaN > 0 fails, camera.ts:165), but pixelConverged's
+    // own guard (NaN <= 0, camera.ts:350) fails as well and the illuminance sums stay 0: the variance
+    // is 0 and every pixel "converges" at the first multiple of aBatch. Only the sequential kernel
+    // asks pixelConverged after every sample.
+    const bool nan_tolerance = std::isnan(C.a_tolerance) && C.samples > 1.0;
+    plan.sequential = prog_len <= 0 && (C.n_samples <= 0 || !chunked || (C.adaptive && !rounds) || nan_tolerance);
     if (plan.sequential) return plan;
 
     // Stage-compacted pool kernel (pt_pool_kernel): possible for product brute-force

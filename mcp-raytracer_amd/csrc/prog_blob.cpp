@@ -44,7 +44,10 @@ ProgBlobHeader prog_parse_blob(const uint8_t* blob, size_t len) {
                                     std::to_string(kProgBlobVersion));
     if (fnv1a(&h, offsetof(ProgBlobHeader, header_checksum)) != h.header_checksum)
         throw std::invalid_argument("progressive blob: corrupt header (checksum mismatch)");
-    const long slots = h.rw > 0 && h.rh > 0 ? (long)((h.rw + kProgTile - 1) / kProgTile) * ((h.rh + kProgTile - 1) / kProgTile) * kProgWave : 0;
+    // (in long: rw + 7 overflows an int for a header that claims a region 2^31 - 1 wide)
+    const long slots = h.rw > 0 && h.rh > 0
+                           ? (((long)h.rw + kProgTile - 1) / kProgTile) * (((long)h.rh + kProgTile - 1) / kProgTile) * kProgWave
+                           : 0;
     if (slots <= 0 || h.payload_bytes != (uint64_t)slots * kProgPixBytes)
         throw std::invalid_argument("progressive blob: corrupt header (payload length does not fit the region)");
     if (len < sizeof(ProgBlobHeader) + h.payload_bytes)

@@ -276,7 +276,18 @@ template <class Real, bool EMIT, bool PROF>
 __device__ __forceinline__ V3 miss_color(const RtCamera& C, const Path<EMIT>& P, unsigned long long& st_err,
                                          Prof& pf) {
     if (!C.has_background) st_err |= ERR_NO_BACKGROUND;
-    const V3 ud = unit<Real>(P.d);
+    V3 ud;
+    if constexpr (sizeof(Real) == 4) {
+        // The fp32 build contracts |d|^2 = x x + y y + z z, and which product it left unfused
+        // depended on the kernel: the sequential kernel rounded x x first, the chunked and pool
+        // kernels y y, and their sky pixels differed in the last bit (about 1 % of them). One
+        // order, spelled out - the chunked and pool kernels' - so all three write the same bits.
+        float l = __builtin_fmaf(P.d.z, P.d.z, __builtin_fmaf(P.d.x, P.d.x, P.d.y * P.d.y));
+        if (l > 0.0f) l = rsqrt_rn<float>(l);
+        ud = V3{P.d.x * l, P.d.y * l, P.d.z * l};
+    } else {
+        ud = unit<Real>(P.d);
+    }
     const Real a = (Real)0.5 * ((Real)ud.y + (Real)1);
     const V3 c = mulv(add(scale<Real>(ld3(C.bg_top), (Real)1 - a), scale<Real>(ld3(C.bg_bottom), a)), P.T);
     psec<PROF>(pf, PR_MISS);

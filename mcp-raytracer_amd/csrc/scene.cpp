@@ -80,9 +80,23 @@ struct Builder {
     }
 
     // createMaterial (src/scenes/scenes.ts:144-180). Returns a material index.
+    // The reference recurses on the JS stack and a material that reaches itself
+    // ends as a RangeError; here the materials being resolved are kept on `resolving`
+    // and re-entry, or more than kMaxMaterialDepth of them, fails with that message.
+    static constexpr size_t kMaxMaterialDepth = 1000;
+    std::vector<const Value*> resolving;
+    struct Resolving {
+        std::vector<const Value*>& s;
+        Resolving(std::vector<const Value*>& st, const Value* md) : s(st) { s.push_back(md); }
+        ~Resolving() { s.pop_back(); }
+    };
+
     int create_material(const Value* ref) {
         const Value* md = resolve(ref);
         if (!md) fail("Material not found: " + js_string(ref));
+        if (resolving.size() >= kMaxMaterialDepth || std::find(resolving.begin(), resolving.end(), md) != resolving.end())
+            fail("Maximum call stack size exceeded (material " + js_string(ref) + ")");
+        Resolving guard(resolving, md);
         const Value* tv = md->get("type");
         const std::string type = tv && tv->is_string() ? tv->str : js_string(tv);
         RtMat m{};
@@ -135,23 +149,30 @@ struct Builder {
 
     // Material.emitted(rec) is a constant per material: DefaultMaterial -> BLACK,
     // DiffuseLight -> emit, Mixed -> E1*w + E2*(1-w), Layered -> inner's.
-    V3 emitted_of(int mi) {
+    // Both walk a material's children, which create_material nests at most
+    // kMaxMaterialDepth deep; `level` holds them to that bound on their own.
+    static void check_level(size_t level) {
+        if (level > kMaxMaterialDepth) fail("Maximum call stack size exceeded (material nesting)");
+    }
+    V3 emitted_of(int mi, size_t level = 1) {
+        check_level(level);
         const RtMat& m = out.mats[mi];
         switch (m.type) {
             case MAT_LIGHT: return v3(m.color[0], m.color[1], m.color[2]);
             case MAT_MIXED: {
-                V3 e1 = scale<double>(emitted_of(m.c0), m.p0);
-                V3 e2 = scale<double>(emitted_of(m.c1), 1.0 - m.p0);
+                V3 e1 = scale<double>(emitted_of(m.c0, level + 1), m.p0);
+                V3 e2 = scale<double>(emitted_of(m.c1, level + 1), 1.0 - m.p0);
                 return add(e1, e2);
             }
-            case MAT_LAYERED: return emitted_of(m.c1);
+            case MAT_LAYERED: return emitted_of(m.c1, level + 1);
             default: return v3(0, 0, 0);
         }
     }
-    bool can_scatter(int mi) {
+    bool can_scatter(int mi, size_t level = 1) {
+        check_level(level);
         const RtMat& m = out.mats[mi];
         if (m.type == MAT_LIGHT) return false;
-        if (m.type == MAT_MIXED) return can_scatter(m.c0) || can_scatter(m.c1);
+        if (m.type == MAT_MIXED) return can_scatter(m.c0, level + 1) || can_scatter(m.c1, level + 1);
         return true;
     }
 
@@ -351,6 +372,15 @@ int32_t loop_threshold(double x) {
     return (int32_t)std::ceil(x);
 }
 
+// RenderOptions.seed -> the RNG's 32-bit seed word: a non-finite number is 0, any other is
+// truncated towards zero and taken modulo 2^32 (so -1 is 0xFFFFFFFF and 2^32 + 5 is 5).
+uint32_t seed_word(double seed) {
+    if (!std::isfinite(seed)) return 0;
+    double m = std::fmod(std::trunc(seed), 4294967296.0);  // exact, inside (-2^32, 2^32)
+    if (m < 0) m += 4294967296.0;
+    return (uint32_t)m;
+}
+
 }  // namespace
 
 SceneBuild build_scene(const Value& scene_data, const Value* render_options) {
@@ -412,6 +442,24 @@ SceneBuild build_scene(const Value& scene_data, const Value* render_options) {
             l.area = vlength(cross<double>(u, v));  // Quad.area = u.cross(v).length()
         }
         b.out.lights.push_back(l);
+    }
+
+    // A throughput that is not finite makes the zero emission of every later hit NaN (0 * NaN,
+    // 0 * inf: emitted.multiplyVec(throughput), camera.ts:261), so such paths need the emission
+    // stack as well. The scene can produce one through a scattering material with a non-finite
+    // colour (the attenuation) or a light whose geometry is not finite (its direction and PDF
+    // value are NaN, and NaN <= 0.0001 does not end the path).
+    for (const RtMat& m : b.out.mats)
+        if ((m.type == MAT_LAMBERT || m.type == MAT_METAL) &&
+            !(std::isfinite(m.color[0]) && std::isfinite(m.color[1]) && std::isfinite(m.color[2])))
+            emissive_scatter = 1;
+    for (const RtLight& l : b.out.lights) {
+        const RtPrim& p = b.out.prims[(size_t)l.prim];
+        bool finite = std::isfinite(p.s0);
+        for (int k = 0; k < 3; ++k)
+            finite = finite && std::isfinite(p.g0[k]) &&
+                     (p.type == PRIM_SPHERE || (std::isfinite(p.g1[k]) && std::isfinite(p.g2[k])));
+        if (!finite) emissive_scatter = 1;
     }
 
     // Camera (src/camera.ts:107-166) with createCameraFromSceneData's option mapping
@@ -509,7 +557,7 @@ SceneBuild build_scene(const Value& scene_data, const Value* render_options) {
     cam.n_nodes = (int32_t)b.out.nodes.size();
     cam.n_prims = (int32_t)b.out.prims.size();
     cam.n_mats = (int32_t)b.out.mats.size();
-    cam.seed = (uint32_t)(int64_t)seed;
+    cam.seed = seed_word(seed);
     cam.seed_mix = splitmix64(cam.seed);
     // fast-traversal tree over the reference's per-object boxes, in slot order (scene_tree.cpp)
     {
@@ -522,7 +570,7 @@ SceneBuild build_scene(const Value& scene_data, const Value* render_options) {
     // a node of level L the stack holds at most 3 (L - 1) entries, so its writes stay below
     // 3 t4depth entries - inside this bound.
     cam.stack_depth = std::max(b.out.bvh_depth, 3 * b.out.t4depth + 1) + 1;
-    b.out.fast_ok = prims_inside_boxes(b.out.prims);
+    b.out.fast_ok = prims_inside_boxes(b.out.prims) && boxes_keep_their_extent(b.boxes, from);
     return std::move(b.out);
 }
 

@@ -36,6 +36,8 @@ struct SceneBuild {
     // Every primitive lies inside its own reference box (no negative / NaN
     // sphere radius, no slightly tilted plane given a thin axis box), so a
     // conservative culling test returns the reference's hit: fast traversal OK.
+    // And every finite box keeps its extent when seen from anywhere in the scene
+    // (scene_tree.cpp boxes_keep_their_extent).
     bool fast_ok = true;
     std::vector<int32_t> prim_object;  // prim slot -> index in SceneData.objects
 };

@@ -294,6 +294,32 @@ bool prims_inside_boxes(const std::vector<RtPrim>& prims) {
     return true;
 }
 
+// AABB.hit subtracts the ray origin from both faces of an axis in doubles (aabb.ts:36-60) and
+// rejects the box when `tmax <= tmin`. From an origin of magnitude M two faces closer than
+// ulp(M) = M 2^-52 round to the same difference: the reference then never enters a box the ray
+// crosses (a camera at y = 1e20 above the floor plane's 2e-4 slab; a sphere whose radius is lost
+// in its centre's fp32 store) while brute force and the fast walk, which do not depend on that
+// box, still hit the primitive. Ray origins are the camera centre and hit points, which lie in
+// the primitives' boxes (or anywhere on an infinite plane: not covered). So every finite extent
+// must be positive and at least 2^10 ulp(M), M the largest finite coordinate of any box or of
+// the centre; a centre that is not finite fails too. Such scenes use the reference-order traversal.
+bool boxes_keep_their_extent(const std::vector<Box>& boxes, V3 center) {
+    double big = 0.0, thin = INFINITY;
+    for (float c : {center.x, center.y, center.z}) {
+        if (!std::isfinite(c)) return false;
+        big = std::max(big, std::fabs((double)c));
+    }
+    for (const Box& b : boxes) {
+        for (int a = 0; a < 3; ++a) {
+            const double lo = comp(b.mn, a), hi = comp(b.mx, a);
+            if (std::isfinite(lo)) big = std::max(big, std::fabs(lo));
+            if (std::isfinite(hi)) big = std::max(big, std::fabs(hi));
+            if (std::isfinite(lo) && std::isfinite(hi)) thin = std::min(thin, hi - lo);
+        }
+    }
+    return thin > 0.0 && thin >= std::ldexp(big, -42);  // (also false for a NaN extent)
+}
+
 void build_fast_tree(SceneBuild& out, const std::vector<Box>& slot_box) {
     // SAH over the reference's per-object boxes (finite boxes only, i.e. no planes), else the
     // reference tree itself

@@ -25,4 +25,8 @@ void build_fast_tree(SceneBuild& out, const std::vector<Box>& slot_box);
 // SceneBuild::fast_ok: every primitive lies inside the box the reference gives it.
 bool prims_inside_boxes(const std::vector<RtPrim>& prims);
 
+// SceneBuild::fast_ok, second condition: the reference's slab test can tell the two faces of
+// every finite box extent apart from any ray origin inside the scene (camera centre included).
+bool boxes_keep_their_extent(const std::vector<Box>& boxes, V3 center);
+
 }  // namespace rt

@@ -133,6 +133,13 @@ double num(const J* v, double dflt) {
     if (v->t == J::NUL) return 0;
     return NAN;
 }
+// RenderOptions.seed -> the RNG's seed word: non-finite is 0, otherwise truncated, modulo 2^32
+uint32_t seed_word(double seed) {
+    if (!std::isfinite(seed)) return 0;
+    double m = std::fmod(std::trunc(seed), 4294967296.0);
+    if (m < 0) m += 4294967296.0;
+    return (uint32_t)m;
+}
 bool truthy(const J* v) {
     if (!v) return false;
     if (v->t == J::NUL) return false;
@@ -703,11 +710,24 @@ template <class R> struct Scene {
     int bvh_depth = 0;
     std::map<std::string, const J*> matmap;
 
+    // createMaterial recurses on the JS stack; a material that reaches itself is a RangeError there.
+    // Here the materials being resolved are kept in `resolving`: re-entry, or more than 1000, throws.
+    std::vector<const J*> resolving;
+    struct Resolving {
+        std::vector<const J*>& s;
+        Resolving(std::vector<const J*>& st, const J* md) : s(st) { s.push_back(md); }
+        ~Resolving() { s.pop_back(); }
+    };
+
     const Material<R>* create_material(const J* ref) {
         const J* md = nullptr;
         if (ref && ref->t == J::STR) { auto it = matmap.find(ref->s); md = it == matmap.end() ? nullptr : it->second; }
         else if (truthy(ref)) md = ref;
         if (!md) throw std::runtime_error("Material not found");
+        if (resolving.size() >= 1000 || std::find(resolving.begin(), resolving.end(), md) != resolving.end())
+            throw std::runtime_error("Maximum call stack size exceeded (material " +
+                                     (ref->t == J::STR ? ref->s : std::string("[object Object]")) + ")");
+        Resolving guard(resolving, md);
         const J* tj = md->at("type");
         std::string type = tj && tj->t == J::STR ? tj->s : "undefined";
         auto vec = [&](const char* k) {
@@ -847,7 +867,7 @@ template <class R> struct Camera {
         roulette = opt("roulette") ? truthy(opt("roulette")) : true;
         rDepth = (R)(opt("rouletteDepth") ? num(opt("rouletteDepth"), NAN) : 3);
         if (const J* m = opt("mode")) { if (m->t == J::STR) mode = m->s == "bounces" ? 1 : (m->s == "samples" ? 2 : 0); }
-        if (const J* s = opt("seed")) seed = (uint32_t)(int64_t)num(s, 0);
+        if (const J* s = opt("seed")) seed = seed_word(num(s, 0));
 
         // Camera arithmetic is always JS doubles; vectors fp32 (host-side, once).
         const J* vf = cd->at("vfov");

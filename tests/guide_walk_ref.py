@@ -89,7 +89,8 @@ def continue_dir(scene, mat, din, n, front, max_fuzz=0.0):
     if kind == "glass":
         return ~none, dielectric_dir(mat["ior"], front, din, n)[0]
     if kind == "mixed":
-        w = max(0.0, min(1.0, float(mat["weight"])))           # MixedMaterial's constructor
+        w = float(mat["weight"])
+        w = w if w != w else max(0.0, min(1.0, w))             # MixedMaterial's constructor (Math.max / min keep a NaN)
         return continue_dir(scene, mat["diff"] if w >= 0.5 else mat["spec"], din, n, front, max_fuzz)
     if kind == "layered":
         d2, reflected = dielectric_dir(material_of(scene, mat["outer"])["ior"], front, din, n)
