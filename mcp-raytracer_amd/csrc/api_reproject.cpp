@@ -10,54 +10,72 @@ using namespace rt;
 
 // The device side of a call once both views' guides and the previous radiance (pb.rad(),
 // region-packed) are there: the previous colour packed as the plain filter packs it, the gather,
-// then history -> nb.nrm(), weight -> nb.dist(), the blend -> nb.rad() / nb.u8. ev (or null):
-// events 2..4, recorded before and after the gather and after the unpack passes. Queued.
-static void rp_run(DnBufs& nb, DnBufs& pb, const RpView& view, const rt_region& r, const rt_region& pr,
-                   const uint8_t* d_reusable, int n_objects, const RpOpts& o, const RpNew& nw, bool want_hist,
-                   bool want_rad, bool want_u8, hipStream_t stream, hipEvent_t* ev) {
+// then history -> nb.nrm(), weight -> nb.dist(), the blend -> nb.rad() / nb.u8 and, through chains,
+// the kind -> ch->d_kind. ev (or null): events 2..4, recorded before and after the gather and after
+// the unpack passes. Queued.
+void rt::rp_run(DnBufs& nb, DnBufs& pb, const RpView& view, const rt_region& r, const rt_region& pr,
+                const uint8_t* d_reusable, int n_objects, const RpOpts& o, const RpNew& nw, bool want_hist, bool want_rad,
+                bool want_u8, hipStream_t stream, hipEvent_t* ev, const RpChain* ch) {
     auto mark = [&](int k) {
         if (ev) hip_check(hipEventRecord(ev[k], stream), "hipEventRecord");
     };
     hip_check(launch_denoise_pack(pb.rad(), pr.width, 0, 0, pr.width, pr.height, pb.gn, 1.0f, nullptr, pb.c0, pb.fn, stream),
               "denoise_pack_kernel");
     mark(2);
-    RpArgs a = gather_args<RpArgs>(view, r, pr, n_objects, o, nw);
-    a.nh = o.nh;
-    hip_check(launch_reproject(a, nw.gn, nw.gp, pb.gn, pb.gp, pb.c0, d_reusable, nw.fresh, nw.pxs, nb.c0,
-                               nw.fresh ? nb.c1.p : nullptr, stream),
-              "reproject_kernel");
+    if (ch) {
+        RsArgs a = gather_args<RsArgs>(view, r, pr, n_objects, o, nw);
+        a.nh = o.nh;
+        a.pp2 = rs_pp2(view, ch->point_pixels);
+        for (int k = 0; k < 3; ++k) a.cn[k] = ch->cn[k];
+        hip_check(launch_reproject_spec(a, ch->ng, ch->pg, pb.c0, d_reusable, ch->d_through, nw.fresh, nw.pxs, nb.c0, nb.c1,
+                                        stream),
+                  "reproject_spec_kernel");
+    } else {
+        RpArgs a = gather_args<RpArgs>(view, r, pr, n_objects, o, nw);
+        a.nh = o.nh;
+        hip_check(launch_reproject(a, nw.gn, nw.gp, pb.gn, pb.gp, pb.c0, d_reusable, nw.fresh, nw.pxs, nb.c0,
+                                   nw.fresh ? nb.c1.p : nullptr, stream),
+                  "reproject_kernel");
+    }
     mark(3);
     const int n = r.width * r.height;
     if (want_hist) hip_check(launch_denoise_unpack(nb.c0, n, nb.nrm(), nullptr, nb.dist(), stream), "denoise_unpack_kernel");
     if (nw.fresh && (want_rad || want_u8))
         hip_check(launch_denoise_unpack(nb.c1, n, want_rad ? nb.rad() : nullptr, want_u8 ? nb.u8.p : nullptr, nullptr, stream),
                   "denoise_unpack_kernel");
+    if (ch && ch->want_kind) hip_check(launch_reproject_spec_kind(nb.c1, n, ch->d_kind, stream), "reproject_spec_kind_kernel");
     mark(4);
 }
 
 // A call's outputs into the caller's arrays, then its one host sync.
-static void rp_outputs(const DnBufs& nb, const RegionIo& io, float* history, float* weight, float* radiance, uint8_t* rgb) {
+void rt::rp_outputs(const DnBufs& nb, const RegionIo& io, float* history, float* weight, float* radiance, uint8_t* rgb,
+                    uint8_t* kind, const uint8_t* d_kind) {
     io.down(history, nb.nrm(), 3 * sizeof(float));
     io.down(weight, nb.dist(), sizeof(float));
     io.down(radiance, nb.rad(), 3 * sizeof(float));
     io.down(rgb, nb.u8, 3);
+    io.down(kind, d_kind, 1);
     hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
 }
 
 // The previous view's side of a camera call, on the current device: its context with the
-// radiance uploaded into rp_prev.rad() and the guide pass queued into rp_prev.gn / gp.
-static DnBufs& rp_prev_side(rt_camera* prev_cam, const rt_region& pr, const float* prev_radiance, hipStream_t stream,
-                            hipEvent_t* ev, const std::function<void()>& new_guides) {
+// radiance uploaded into rp_prev.rad() and the guide pass queued into rp_prev.gn / gp; with `go`,
+// also the guide pass through the chain into its rs_prev.
+DevCtx& rt::rp_prev_side(rt_camera* prev_cam, const rt_region& pr, const float* prev_radiance, hipStream_t stream,
+                         hipEvent_t* ev, const std::function<void()>& new_guides, const rt_guide_options* go) {
     DevCtx& p = prev_cam->current();
     p.ensure_device();
     DnBufs& pb = p.rp_prev;
-    pb.ensure((size_t)pr.width * pr.height);
+    const size_t n = (size_t)pr.width * pr.height;
+    pb.ensure(n);
+    if (go) p.rs_prev.ensure(n);
     RegionIo{prev_cam->build.cam.width, pr, stream}.up(pb.rad(), prev_radiance, 3 * sizeof(float));
     hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
     new_guides();
     p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{pb.gn, pb.gp}, stream);
+    if (go) p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{p.rs_prev.sgn, p.rs_prev.sgp}, stream, go, p.rs_prev.chain);
     hip_check(hipEventRecord(ev[1], stream), "hipEventRecord");
-    return pb;
+    return p;
 }
 
 extern "C" {
@@ -151,7 +169,7 @@ int rt_camera_reproject(rt_camera* cam, const rt_region* region, rt_camera* prev
         if (radiance && px_samples) io.up(nb.obj, px_samples, sizeof(int32_t));
         DnBufs& pb = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] {
             c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{nb.gn, nb.gp}, stream);
-        });
+        }).rp_prev;
         const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
                        io.r.width, 0, 0, (float)samples};
         rp_run(nb, pb, rp_camera_view(prev_cam), io.r, pr, d_reusable, C.n_prims, o, nw, history_out || weight_out,
@@ -181,7 +199,7 @@ int rt_camera_progressive_reproject(rt_camera* cam, rt_camera* prev_cam, const r
         nb.ensure((size_t)io.n());
         hipEvent_t* ev = c.rp_events();
         const uint8_t* d_reusable = c.ensure_reusable();
-        DnBufs& pb = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] { session_guides(cam, c, stream); });
+        DnBufs& pb = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] { session_guides(cam, c, stream); }).rp_prev;
         const RpNew nw{P.d_gn, P.d_gp, P.d_rad, P.d_pxs, C.width, io.r.x, io.r.y, 0.0f};
         rp_run(nb, pb, rp_camera_view(prev_cam), io.r, pr, d_reusable, C.n_prims, o, nw, weight_out != nullptr,
                radiance != nullptr, rgb != nullptr, stream, ev);

@@ -158,9 +158,7 @@ int rt_camera_progressive_accumulate(rt_camera* cam, rt_history* h, const rt_tem
         if (!h->d_reusable || h->views == 0) {  // (an uncommitted call may have been another scene's)
             std::vector<uint8_t> t = cam->reusable_objects();
             h->n_objects = (int32_t)t.size();
-            t.resize(std::max<size_t>(t.size(), 1), 0);
-            h->d_reusable.ensure(t.size(), "hipMalloc(reusable objects)");
-            hip_check(hipMemcpy(h->d_reusable, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+            upload_table(h->d_reusable, std::move(t), "hipMalloc(reusable objects)");
         }
         DnBufs& b = c.dn;
         b.ensure(n);

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <stdexcept>
 
+#include "pass_host.hpp"
 #include "prog_blob.hpp"
 
 namespace rt {
@@ -562,12 +563,7 @@ hipEvent_t* DevCtx::rp_events() {
 }
 
 const uint8_t* DevCtx::ensure_reusable() {
-    if (!d_reusable) {
-        std::vector<uint8_t> t = host.reusable_objects();
-        t.resize(std::max<size_t>(t.size(), 1), 0);
-        d_reusable.ensure(t.size(), "hipMalloc(reusable objects)");
-        hip_check(hipMemcpy(d_reusable, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
-    }
+    if (!d_reusable) upload_table(d_reusable, host.reusable_objects(), "hipMalloc(reusable objects)");
     return d_reusable;
 }
 

@@ -86,6 +86,19 @@ void upload_reusable(DevBuf<uint8_t>& d, const uint8_t* reusable, int32_t n_obje
         hip_check(hipMemcpyAsync(d, reusable, (size_t)n_objects, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
 }
 
+void upload_table(DevBuf<uint8_t>& d, std::vector<uint8_t> t, const char* what) {
+    t.resize(std::max<size_t>(t.size(), 1), 0);
+    d.ensure(t.size(), what);
+    hip_check(hipMemcpy(d, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+}
+
+SpecOpts spec_resolve(float point_pixels, int32_t through, const std::string& who) {
+    SpecOpts r{resolve_field(point_pixels, 4.0f, who, "point_pixels"), 0};
+    if (through < 0 || through > 15) throw std::invalid_argument(who + ": through must be a mask in 0..15 (0: the default, 15)");
+    r.through = through ? through : 15;
+    return r;
+}
+
 void session_radiance(rt_camera* cam, const std::string& who) {
     if (cam->build.cam.mode != MODE_DEFAULT)
         throw std::invalid_argument(who + ": the frames of mode bounces / samples are not radiance");

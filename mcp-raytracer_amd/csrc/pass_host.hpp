@@ -4,10 +4,12 @@
 // head of the gather kernels' arguments.
 #pragma once
 
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "api_call.hpp"
+#include "reproject_spec.hpp"
 
 namespace rt {
 
@@ -61,6 +63,9 @@ void upload_guides(DnBufs& b, const RegionIo& io, const float* normal, const flo
 
 // The caller's reusable table (n_objects >= 0 entries) into d, at least one byte. Queued.
 void upload_reusable(DevBuf<uint8_t>& d, const uint8_t* reusable, int32_t n_objects, hipStream_t stream);
+// A per-object table the host built (reusable or through objects) into d, at least one byte: an
+// empty table is one zero. `what` names the allocation. Done on return.
+void upload_table(DevBuf<uint8_t>& d, std::vector<uint8_t> t, const char* what);
 
 // The open session's frames must be radiance.
 void session_radiance(rt_camera* cam, const std::string& who);
@@ -132,6 +137,32 @@ Args gather_args(const RpView& view, const rt_region& r, const rt_region& pr, in
     return a;
 }
 
+// ---- what the reprojection's two ABI units share (api_reproject.cpp) -------------------------------
+// What a call through specular chains adds to the plain one: both views' guide planes, the new
+// view's centre, the through table, point_pixels resolved and the kind plane.
+struct RpChain {
+    RsGuides ng, pg;
+    const float* cn;
+    const uint8_t* d_through;
+    float point_pixels;
+    uint8_t* d_kind;
+    bool want_kind;
+};
+// The device side of a call once both views' guides and the previous radiance (pb.rad(),
+// region-packed) are there: the pack pass, the gather (ch: through chains), the unpack passes. ev
+// (or null): events 2..4. Queued.
+void rp_run(DnBufs& nb, DnBufs& pb, const RpView& view, const rt_region& r, const rt_region& pr, const uint8_t* d_reusable,
+            int n_objects, const RpOpts& o, const RpNew& nw, bool want_hist, bool want_rad, bool want_u8, hipStream_t stream,
+            hipEvent_t* ev, const RpChain* ch = nullptr);
+// A call's outputs into the caller's arrays, then its one host sync.
+void rp_outputs(const DnBufs& nb, const RegionIo& io, float* history, float* weight, float* radiance, uint8_t* rgb,
+                uint8_t* kind = nullptr, const uint8_t* d_kind = nullptr);
+// The previous view's side of a camera call: its context on the current device, the radiance
+// uploaded into its rp_prev (event 0), new_guides(), its guide pass - with `go` also the one
+// through the chain into its rs_prev - (event 1). Queued.
+DevCtx& rp_prev_side(rt_camera* prev_cam, const rt_region& pr, const float* prev_radiance, hipStream_t stream,
+                     hipEvent_t* ev, const std::function<void()>& new_guides, const rt_guide_options* go = nullptr);
+
 // ---- what the accumulation's two ABI units share (api_temporal.cpp) --------------------------------
 // rt_temporal_options resolved: a zero field = the default; levels 0 = no filter.
 struct TpOpts : GatherOpts {
@@ -154,6 +185,13 @@ void tp_outputs(const DnBufs& b, const RegionIo& io, float* radiance, uint8_t* r
                 float* weight);
 
 // ---- what the two specular ABI units share (reproject_spec_api.cpp) --------------------------------
+// The two fields rt_specular_reproject_options and rt_specular_temporal_options add to their base,
+// resolved: a zero field = the default.
+struct SpecOpts {
+    float point_pixels;
+    int32_t through;
+};
+SpecOpts spec_resolve(float point_pixels, int32_t through, const std::string& who);
 // The guide options of a call: NULL = the specular walk's defaults; first-hit guides have no chains.
 rt_guide_options rs_guide_options(const rt_guide_options* go, const std::string& who);
 // through[o] for the mask and max_fuzz, as rt_camera_through_objects returns it.

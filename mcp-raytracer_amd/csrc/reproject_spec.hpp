@@ -9,7 +9,8 @@
 // All device arrays are REGION-PACKED as in denoise.hpp. Per view the kernel reads the first-hit
 // pair gn / gp, the pair through the chain sgn / sgp (both walked with one rt_guide_options) and
 // the chain word; of the previous view also the colour {r, g, b, finite flag} as the plain filter's
-// pack pass writes it. The projection arithmetic is reproject.hip's, copied (as temporal.hip's is).
+// pack pass writes it. The projection, the tap walk and the tap tests are gather.hpp's, shared with
+// reproject.hip and the two accumulation units.
 // No reference counterpart: the reference renders every frame from scratch.
 #pragma once
 
@@ -35,36 +36,6 @@ struct RsGuides {
     const float4 *sgn, *sgp;  // through the chain
     const int32_t* chain;
 };
-
-#ifdef __HIPCC__
-__device__ __forceinline__ bool rs_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ float rs_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
-
-// What a k >= 1 pixel asks of a tap: its chain guides {n, P with the object bits}, its first
-// object and chain word, and the two bounds plane = sigma_plane Ds, point = (pp2 Ds) Ds.
-struct RsChainPixel {
-    float4 n, P;
-    int32_t o1, ch;
-    float plane, point;
-};
-
-// The tap test of a k >= 1 pixel: the previous pixel walked the same chain (equal chain word, first
-// and last object), its radiance is finite, and its chain guides {nq, Pq} show the same surface
-// point - the normal and plane checks of reproject.hip on the chain guides, and the point check
-// |Pq - P|^2 <= point. pfirst: the previous first-hit gp; cq.w: the pack pass's finite flag.
-// (every comparison is false for a NaN)
-__device__ __forceinline__ bool rs_chain_tap_counts(const RsChainPixel& p, float normal_min, const float4& pfirst,
-                                                    const float4& nq, const float4& Pq, const float4& cq, int32_t chq) {
-    const float ex = Pq.x - p.P.x, ey = Pq.y - p.P.y, ez = Pq.z - p.P.z;
-    const float dn = rs_dot(p.n.x, p.n.y, p.n.z, nq.x, nq.y, nq.z);
-    const float e = rs_dot(p.n.x, p.n.y, p.n.z, ex, ey, ez);
-    const float qq = rs_dot(ex, ey, ez, ex, ey, ez);
-    return chq == p.ch && __float_as_int(pfirst.w) == p.o1 && __float_as_int(Pq.w) == __float_as_int(p.P.w) &&
-           cq.w != 0.0f && dn >= normal_min && fabsf(e) <= p.plane && qq <= p.point;
-}
-#endif
 
 // One thread per pixel of the new region. through: object index -> 1 where a chain may start.
 // hist = {history.rgb, weight}; outc = {blend.rgb (zero without `fresh`), kind as a float: 0 no

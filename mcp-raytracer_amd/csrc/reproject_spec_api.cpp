@@ -10,19 +10,14 @@
 using namespace rt;
 
 // rt_specular_reproject_options resolved: a zero field = the default.
-struct RsOpts {
+struct RsOpts : SpecOpts {
     RpOpts base;
-    float point_pixels;
-    int32_t through;
 };
 static RsOpts rs_resolve(const rt_specular_reproject_options* o, const std::string& who) {
     rt_specular_reproject_options z{};
     if (o) z = *o;
-    RsOpts r{rp_resolve(&z.base, who), 0.0f, 0};
-    r.point_pixels = resolve_field(z.point_pixels, 4.0f, who, "point_pixels");
-    if (z.through < 0 || z.through > 15) throw std::invalid_argument(who + ": through must be a mask in 0..15 (0: the default, 15)");
-    r.through = z.through ? z.through : 15;
-    return r;
+    const RpOpts base = rp_resolve(&z.base, who);  // (its errors first)
+    return RsOpts{spec_resolve(z.point_pixels, z.through, who), base};
 }
 
 // The guide options of a call: NULL = the specular walk's defaults; first-hit guides have no chains.
@@ -62,10 +57,7 @@ static void through_check(const std::string& who, int32_t mask, float max_fuzz) 
 // The table on the device, rebuilt when the mask or max_fuzz change.
 static const uint8_t* ensure_through(DevCtx& c, int32_t mask, float max_fuzz) {
     if (!c.d_through || c.through_mask != mask || c.through_fuzz != max_fuzz) {
-        std::vector<uint8_t> t = through_objects(c.host, mask, max_fuzz);
-        t.resize(std::max<size_t>(t.size(), 1), 0);
-        c.d_through.ensure(t.size(), "hipMalloc(through objects)");
-        hip_check(hipMemcpy(c.d_through, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        upload_table(c.d_through, through_objects(c.host, mask, max_fuzz), "hipMalloc(through objects)");
         c.through_mask = mask;
         c.through_fuzz = max_fuzz;
     }
@@ -85,65 +77,9 @@ float rt::rs_pp2(const RpView& v, float pp) {
     return p2 * pix2;
 }
 
-// The device side of a call once both views' guide planes and the previous radiance (pb.rad(),
-// region-packed) are there: the previous colour packed, the gather, then history -> nb.nrm(),
-// weight -> nb.dist(), the blend -> nb.rad() / nb.u8, kind -> d_kind. ev (or null): events 2..4 as
-// rt_camera_reproject's. Queued.
-static void rs_run(DnBufs& nb, DnBufs& pb, const RsGuides& ng, const RsGuides& pg, uint8_t* d_kind, const RpView& view,
-                   const float* cn, const rt_region& r, const rt_region& pr, const uint8_t* d_reusable,
-                   const uint8_t* d_through, int n_objects, const RsOpts& o, const RpNew& nw, bool want_hist, bool want_rad,
-                   bool want_u8, bool want_kind, hipStream_t stream, hipEvent_t* ev) {
-    auto mark = [&](int k) {
-        if (ev) hip_check(hipEventRecord(ev[k], stream), "hipEventRecord");
-    };
-    hip_check(launch_denoise_pack(pb.rad(), pr.width, 0, 0, pr.width, pr.height, pg.gn, 1.0f, nullptr, pb.c0, pb.fn, stream),
-              "denoise_pack_kernel");
-    mark(2);
-    RsArgs a = gather_args<RsArgs>(view, r, pr, n_objects, o.base, nw);
-    a.nh = o.base.nh;
-    a.pp2 = rs_pp2(view, o.point_pixels);
-    for (int k = 0; k < 3; ++k) a.cn[k] = cn[k];
-    hip_check(launch_reproject_spec(a, ng, pg, pb.c0, d_reusable, d_through, nw.fresh, nw.pxs, nb.c0, nb.c1, stream),
-              "reproject_spec_kernel");
-    mark(3);
-    const int n = r.width * r.height;
-    if (want_hist) hip_check(launch_denoise_unpack(nb.c0, n, nb.nrm(), nullptr, nb.dist(), stream), "denoise_unpack_kernel");
-    if (nw.fresh && (want_rad || want_u8))
-        hip_check(launch_denoise_unpack(nb.c1, n, want_rad ? nb.rad() : nullptr, want_u8 ? nb.u8.p : nullptr, nullptr, stream),
-                  "denoise_unpack_kernel");
-    if (want_kind) hip_check(launch_reproject_spec_kind(nb.c1, n, d_kind, stream), "reproject_spec_kind_kernel");
-    mark(4);
-}
-
-// A call's outputs into the caller's arrays, then its one host sync.
-static void rs_outputs(const DnBufs& nb, const uint8_t* d_kind, const RegionIo& io, float* history, float* weight,
-                       float* radiance, uint8_t* rgb, uint8_t* kind) {
-    io.down(history, nb.nrm(), 3 * sizeof(float));
-    io.down(weight, nb.dist(), sizeof(float));
-    io.down(radiance, nb.rad(), 3 * sizeof(float));
-    io.down(rgb, nb.u8, 3);
-    io.down(kind, d_kind, 1);
-    hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
-}
-
-// The previous view's side of a camera call, on the current device: its context with the radiance
-// uploaded into rp_prev.rad() and both guide passes queued into rp_prev.gn / gp and rs_prev.
-static RsGuides rs_prev_side(rt_camera* prev_cam, const rt_region& pr, const float* prev_radiance,
-                             const rt_guide_options& go, hipStream_t stream, hipEvent_t* ev,
-                             const std::function<void()>& new_guides) {
-    DevCtx& p = prev_cam->current();
-    p.ensure_device();
-    DnBufs& pb = p.rp_prev;
-    const size_t n = (size_t)pr.width * pr.height;
-    pb.ensure(n);
-    p.rs_prev.ensure(n);
-    RegionIo{prev_cam->build.cam.width, pr, stream}.up(pb.rad(), prev_radiance, 3 * sizeof(float));
-    hip_check(hipEventRecord(ev[0], stream), "hipEventRecord");
-    new_guides();
-    p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{pb.gn, pb.gp}, stream);
-    p.launch_guide_pass(pr, prev_cam->traversal, DenoiseGuides{p.rs_prev.sgn, p.rs_prev.sgp}, stream, &go, p.rs_prev.chain);
-    hip_check(hipEventRecord(ev[1], stream), "hipEventRecord");
-    return RsGuides{pb.gn, pb.gp, p.rs_prev.sgn, p.rs_prev.sgp, p.rs_prev.chain};
+// The previous view's guide planes after rp_prev_side walked them.
+static RsGuides prev_guides(const DevCtx& p) {
+    return RsGuides{p.rp_prev.gn, p.rp_prev.gp, p.rs_prev.sgn, p.rs_prev.sgp, p.rs_prev.chain};
 }
 
 extern "C" {
@@ -221,9 +157,10 @@ int rt_reproject_specular(int32_t width, int32_t height, const rt_region* region
         const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
                        io.r.width, 0, 0, (float)samples};
         const RsGuides ng{nb.gn, nb.gp, ns.gn, ns.gp, ns.obj}, pg{pb.gn, pb.gp, ps.gn, ps.gp, ps.obj};
-        rs_run(nb, pb, ng, pg, ns.u8, pv, view->center, io.r, pio.r, d_reusable, d_through, n_objects, o, nw,
-               history_out || weight_out, radiance_out != nullptr, rgb_out != nullptr, kind_out != nullptr, stream, nullptr);
-        rs_outputs(nb, ns.u8, io, history_out, weight_out, radiance_out, rgb_out, kind_out);
+        const RpChain ch{ng, pg, view->center, d_through, o.point_pixels, ns.u8, kind_out != nullptr};
+        rp_run(nb, pb, pv, io.r, pio.r, d_reusable, n_objects, o.base, nw, history_out || weight_out,
+               radiance_out != nullptr, rgb_out != nullptr, stream, nullptr, &ch);
+        rp_outputs(nb, io, history_out, weight_out, radiance_out, rgb_out, kind_out, ns.u8);
     });
 }
 
@@ -252,18 +189,18 @@ int rt_camera_reproject_specular(rt_camera* cam, const rt_region* region, rt_cam
         const uint8_t* d_through = ensure_through(c, o.through, go.max_fuzz);
         if (radiance) io.up(nb.rad(), radiance, 3 * sizeof(float));
         if (radiance && px_samples) io.up(nb.obj, px_samples, sizeof(int32_t));
-        const RsGuides pg = rs_prev_side(prev_cam, pr, prev_radiance, go, stream, ev, [&] {
+        DevCtx& p = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] {
             c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{nb.gn, nb.gp}, stream);
             c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{c.rs.sgn, c.rs.sgp}, stream, &go, c.rs.chain);
-        });
+        }, &go);
         const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
                        io.r.width, 0, 0, (float)samples};
-        const RsGuides ng{nb.gn, nb.gp, c.rs.sgn, c.rs.sgp, c.rs.chain};
-        rs_run(nb, prev_cam->current().rp_prev, ng, pg, c.rs.kind, rp_camera_view(prev_cam), C.center, io.r, pr, d_reusable,
-               d_through, C.n_prims, o, nw, history_out || weight_out, radiance_out != nullptr, rgb_out != nullptr,
-               kind_out != nullptr, stream, ev);
+        const RpChain ch{{nb.gn, nb.gp, c.rs.sgn, c.rs.sgp, c.rs.chain}, prev_guides(p), C.center, d_through,
+                         o.point_pixels, c.rs.kind, kind_out != nullptr};
+        rp_run(nb, p.rp_prev, rp_camera_view(prev_cam), io.r, pr, d_reusable, C.n_prims, o.base, nw,
+               history_out || weight_out, radiance_out != nullptr, rgb_out != nullptr, stream, ev, &ch);
         c.rp_timed = true;
-        rs_outputs(nb, c.rs.kind, io, history_out, weight_out, radiance_out, rgb_out, kind_out);
+        rp_outputs(nb, io, history_out, weight_out, radiance_out, rgb_out, kind_out, c.rs.kind);
     });
 }
 
@@ -291,17 +228,17 @@ int rt_camera_progressive_reproject_specular(rt_camera* cam, rt_camera* prev_cam
         hipEvent_t* ev = c.rp_events();
         const uint8_t* d_reusable = c.ensure_reusable();
         const uint8_t* d_through = ensure_through(c, o.through, go.max_fuzz);
-        const RsGuides pg = rs_prev_side(prev_cam, pr, prev_radiance, go, stream, ev, [&] {
+        DevCtx& p = rp_prev_side(prev_cam, pr, prev_radiance, stream, ev, [&] {
             session_guides(cam, c, stream);
             session_specular_guides(cam, c, go, stream, true);
-        });
+        }, &go);
         const RpNew nw{P.d_gn, P.d_gp, P.d_rad, P.d_pxs, C.width, io.r.x, io.r.y, 0.0f};
-        const RsGuides ng{P.d_gn, P.d_gp, P.d_sgn, P.d_sgp, P.d_sch};
-        rs_run(nb, prev_cam->current().rp_prev, ng, pg, c.rs.kind, rp_camera_view(prev_cam), C.center, io.r, pr, d_reusable,
-               d_through, C.n_prims, o, nw, weight_out != nullptr, radiance != nullptr, rgb != nullptr, kind_out != nullptr,
-               stream, ev);
+        const RpChain ch{{P.d_gn, P.d_gp, P.d_sgn, P.d_sgp, P.d_sch}, prev_guides(p), C.center, d_through, o.point_pixels,
+                         c.rs.kind, kind_out != nullptr};
+        rp_run(nb, p.rp_prev, rp_camera_view(prev_cam), io.r, pr, d_reusable, C.n_prims, o.base, nw, weight_out != nullptr,
+               radiance != nullptr, rgb != nullptr, stream, ev, &ch);
         c.rp_timed = true;
-        rs_outputs(nb, c.rs.kind, io, nullptr, weight_out, radiance, rgb, kind_out);
+        rp_outputs(nb, io, nullptr, weight_out, radiance, rgb, kind_out, c.rs.kind);
     });
 }
 

@@ -5,8 +5,9 @@
 // history's taps on the chain planes the history keeps of its view; a tap counts where
 // reproject_spec.hpp's chain test holds with temporal.hpp's colour and length conditions in place
 // of the finite flag. The sums, the min_weight cut and the blend by the gathered length and
-// variance are temporal.hpp's. tests/specular_temporal_ref.py is the normative definition; the
-// device result equals it in every bit.
+// variance are temporal.hpp's; one copy of each of these pieces is in gather.hpp.
+// tests/specular_temporal_ref.py is the normative definition; the device result equals it in
+// every bit.
 // All device arrays are REGION-PACKED as in denoise.hpp. The kernel writes temporal.hpp's TpOut
 // and the kind plane (uint8: 0 no history, 1 first hit, 2 chain) directly - no staging plane.
 // No reference counterpart: the reference renders every frame from scratch.
@@ -38,25 +39,6 @@ struct TsHistory {
     const float4* col;
     const float* var;
 };
-
-#ifdef __HIPCC__
-// The variance filter's rule: not (v >= 0 and finite) -> 0.
-__device__ __forceinline__ float ts_variance(float v) { return v >= 0.0f && rs_finite(v) ? v : 0.0f; }
-
-// The tap test of a k >= 1 pixel: rs_chain_tap_counts with the accumulation's colour and length
-// conditions - cq = {r, g, b, length}, all finite, the length > 0 - in place of the finite flag.
-// (every comparison is false for a NaN)
-__device__ __forceinline__ bool ts_chain_tap_counts(const RsChainPixel& p, float normal_min, const float4& pfirst,
-                                                    const float4& nq, const float4& Pq, const float4& cq, int32_t chq) {
-    const float ex = Pq.x - p.P.x, ey = Pq.y - p.P.y, ez = Pq.z - p.P.z;
-    const float dn = rs_dot(p.n.x, p.n.y, p.n.z, nq.x, nq.y, nq.z);
-    const float e = rs_dot(p.n.x, p.n.y, p.n.z, ex, ey, ez);
-    const float qq = rs_dot(ex, ey, ez, ex, ey, ez);
-    return chq == p.ch && __float_as_int(pfirst.w) == p.o1 && __float_as_int(Pq.w) == __float_as_int(p.P.w) &&
-           rs_finite(cq.x) && rs_finite(cq.y) && rs_finite(cq.z) && dn >= normal_min && fabsf(e) <= p.plane &&
-           qq <= p.point && rs_finite(cq.w) && cq.w > 0.0f;
-}
-#endif
 
 // One thread per pixel of the new region. nw: the new view's first-hit pair, chain pair and chain
 // words; through: object index -> 1 where a chain may start; px_samples may be null (the scalar

@@ -11,19 +11,14 @@
 using namespace rt;
 
 // rt_specular_temporal_options resolved: a zero field = the default.
-struct TsOpts {
+struct TsOpts : SpecOpts {
     TpOpts base;
-    float point_pixels;
-    int32_t through;
 };
 static TsOpts ts_resolve(const rt_specular_temporal_options* o, const std::string& who) {
     rt_specular_temporal_options z{};
     if (o) z = *o;
-    TsOpts r{tp_resolve(&z.base, who), 0.0f, 0};
-    r.point_pixels = resolve_field(z.point_pixels, 4.0f, who, "point_pixels");
-    if (z.through < 0 || z.through > 15) throw std::invalid_argument(who + ": through must be a mask in 0..15 (0: the default, 15)");
-    r.through = z.through ? z.through : 15;
-    return r;
+    const TpOpts base = tp_resolve(&z.base, who);  // (its errors first)
+    return TsOpts{spec_resolve(z.point_pixels, z.through, who), base};
 }
 
 static bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
@@ -97,15 +92,10 @@ int rt_camera_progressive_accumulate_specular(rt_camera* cam, rt_history* h, con
         if (!h->d_reusable || h->views == 0) {  // (an uncommitted call may have been another scene's)
             std::vector<uint8_t> t = cam->reusable_objects();
             h->n_objects = (int32_t)t.size();
-            t.resize(std::max<size_t>(t.size(), 1), 0);
-            h->d_reusable.ensure(t.size(), "hipMalloc(reusable objects)");
-            hip_check(hipMemcpy(h->d_reusable, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+            upload_table(h->d_reusable, std::move(t), "hipMalloc(reusable objects)");
         }
         if (!h->d_through || h->views == 0 || h->through_mask != o.through || !same_bits(h->through_fuzz, go.max_fuzz)) {
-            std::vector<uint8_t> t = through_objects(*cam, o.through, go.max_fuzz);
-            t.resize(std::max<size_t>(t.size(), 1), 0);
-            h->d_through.ensure(t.size(), "hipMalloc(through objects)");
-            hip_check(hipMemcpy(h->d_through, t.data(), t.size(), hipMemcpyHostToDevice), "hipMemcpy");
+            upload_table(h->d_through, through_objects(*cam, o.through, go.max_fuzz), "hipMalloc(through objects)");
             h->through_mask = o.through;
             h->through_fuzz = go.max_fuzz;
         }

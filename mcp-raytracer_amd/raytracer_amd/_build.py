@@ -107,7 +107,7 @@ _UNITS = [
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene_types.hpp", "scene.hpp", "scene_js.hpp", "scene_tree.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
             "pt_brute.hpp", "pt_shade.hpp", "pt_pixel.hpp", "pt_kernels.hpp", "pt_pool.hpp", "pt_dispatch.hpp",
             "launch.hpp", "progressive.hpp", "denoise.hpp",
-            "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "temporal_spec.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
+            "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "temporal_spec.hpp", "gather.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp", "api_call.hpp", "pass_host.hpp"]
 _LIBS = ["-lz"]
 

@@ -182,6 +182,36 @@ def test_each_output_alone_is_the_all_outputs_call_on_the_synthetic_pair(rt, gpu
         assert all(bits_equal(one[k], full[k]).all() for k in keys), keys
 
 
+BANDS = (slice(0, 64), slice(64, 128), slice(128, 130))   # the workgroup columns of a 130-pixel row
+
+
+@functools.lru_cache(maxsize=None)
+def wide_pair():
+    """The two planes on a 9 x 130 new view - three workgroup columns of 64 pixels, the last one
+    partial, and three row groups of 4 - against a previous view of another shape, 11 x 120. The
+    new view's last row and the previous view's first are misses."""
+    rng = np.random.default_rng(23)
+    pview, pd = _pinhole((11, 120), (0, 0, 0), 0.02)
+    view, d = _pinhole((9, 130), (-0.11, 0.02, 0.05), 0.018)
+    pg = _two_planes(pview, pd, slice(0, 1))
+    g = _two_planes(view, d, slice(8, 9))
+    prad = (rng.random((11, 120, 3), dtype=F) * F(4)).astype(F)
+    fresh = (rng.random((9, 130, 3), dtype=F) * F(4)).astype(F)
+    prad[4, 70, 1] = np.nan; fresh[3, 129, 2] = np.nan; fresh[5, 64, 0] = np.inf
+    for a in (prad, fresh, *g.values(), *pg.values()):
+        a.setflags(write=False)
+    return g, pview, pg, prad, fresh, np.array([1, 1, 0], np.uint8)
+
+
+def test_a_9x130_frame_spans_three_workgroup_columns(rt, gpu):
+    g, pview, pg, prad, fresh, reusable = wide_pair()
+    kw = dict(reusable=reusable, radiance=fresh, samples=3)
+    want = reproject_ref(prad, pview, pg, **g, **kw)
+    has = want["weight"] > 0
+    assert all(has[:, b].any() and not has[:, b].all() for b in BANDS)
+    assert_is_restatement(lambda **o: rt.reproject(prad, pview, pg, **g, **kw, **o), want, fresh, None, "synthetic 9x130")
+
+
 # ---- 2. the camera entry ---------------------------------------------------------------------------
 CAMERA_CASES = {
     "cornell40": ({"type": "cornell"}, {"width": 40, "samples": 8, "depth": 8, "aTolerance": 0}, "brute"),

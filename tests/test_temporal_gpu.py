@@ -172,6 +172,43 @@ def test_explicit_buffers_on_synthetic_pairs_of_views(rt, gpu, pair, opts, count
         assert bits_equal(plain["length"], want["length"]).all() and bits_equal(plain["weight"], want["weight"]).all()
 
 
+BANDS = (slice(0, 64), slice(64, 128), slice(128, 130))   # the workgroup columns of a 130-pixel row
+
+
+@functools.lru_cache(maxsize=None)
+def wide_pair():
+    """The two planes on a 9 x 130 new view - three workgroup columns of 64 pixels, the last one
+    partial, and three row groups of 4 - against a history of another shape, 11 x 120. The new
+    view's last row and the history's first are misses."""
+    rng = np.random.default_rng(23)
+    shape, pshape = (9, 130), (11, 120)
+    pview, pd = _pinhole(pshape, (0, 0, 0), 0.02)
+    view, d = _pinhole(shape, (-0.11, 0.02, 0.05), 0.018)
+    pg = _two_planes(pview, pd, slice(0, 1))
+    g = _two_planes(view, d, slice(8, 9))
+    prad = (rng.random((*pshape, 3), dtype=F) * F(4)).astype(F)
+    fresh = (rng.random((*shape, 3), dtype=F) * F(4)).astype(F)
+    prad[4, 70, 1] = np.nan; fresh[3, 129, 2] = np.nan; fresh[5, 64, 0] = np.inf
+    plen, pvar, var = _planes(rng, shape, pshape)
+    for a in (prad, fresh, plen, pvar, var, *g.values(), *pg.values()):
+        a.setflags(write=False)
+    hist = {"view": pview, "region": None, "guides": pg, "radiance": prad, "variance": pvar, "length": plen}
+    return g, hist, fresh, var, np.array([1, 1, 0], np.uint8)
+
+
+def test_a_9x130_frame_spans_three_workgroup_columns(rt, gpu):
+    g, hist, fresh, var, reusable = wide_pair()
+    kw = dict(reusable=reusable, radiance=fresh, variance=var, samples=3)
+    want = temporal_ref(hist, **g, **kw)
+    has = want["weight"] > 0
+    assert all(has[:, b].any() and not has[:, b].all() for b in BANDS)
+    out = sentinels(9, 130)
+    rt.temporal_accumulate(hist["radiance"], hist["variance"], hist["length"], hist["view"], hist["guides"], **g,
+                           rgb=out["rgb"], out=out["radiance"], variance_out=out["variance"], length_out=out["length"],
+                           weight_out=out["weight"], **kw)
+    assert_outputs(out, want, None, "synthetic 9x130")
+
+
 @pytest.mark.parametrize("levels", [0, 2], ids=["unfiltered", "filter2"])
 def test_each_output_alone_is_the_all_outputs_call_on_the_small_pair(rt, gpu, levels):
     """The raw entry with one output pointer at a time (the outputs gate the filter and which
