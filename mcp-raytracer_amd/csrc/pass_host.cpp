@@ -80,6 +80,29 @@ void upload_guides(DnBufs& b, const RegionIo& io, const float* normal, const flo
               "guides_pack_kernel");
 }
 
+void upload_views(DnBufs& nb, DnBufs& ns, const RegionIo& io, const HostGuides& g, DnBufs& pb, DnBufs& ps,
+                  const RegionIo& pio, const HostGuides& pg, RsGuides* ng, RsGuides* pgd) {
+    struct V {
+        DnBufs &b, &s;
+        const RegionIo& io;
+        const HostGuides& g;
+    } views[] = {{nb, ns, io, g}, {pb, ps, pio, pg}};
+    for (V& v : views) {
+        v.b.ensure((size_t)v.io.n());
+        if (v.g.chain_normal) v.s.ensure((size_t)v.io.n());
+    }
+    for (V& v : views) {
+        upload_guides(v.b, v.io, v.g.normal, v.g.position, v.g.distance, v.g.object);
+        if (v.g.chain_normal)
+            upload_guides(v.s, v.io, v.g.chain_normal, v.g.chain_position, v.g.chain_distance, v.g.chain_object);
+    }
+    // (the chain guides are packed: their object planes now carry the chain words)
+    for (V& v : views)
+        if (v.g.chain_normal) v.io.up(v.s.obj, v.g.chain, sizeof(int32_t));
+    *ng = g.chain_normal ? RsGuides{nb.gn, nb.gp, ns.gn, ns.gp, ns.obj} : RsGuides{nb.gn, nb.gp, nullptr, nullptr, nullptr};
+    *pgd = pg.chain_normal ? RsGuides{pb.gn, pb.gp, ps.gn, ps.gp, ps.obj} : RsGuides{pb.gn, pb.gp, nullptr, nullptr, nullptr};
+}
+
 void upload_reusable(DevBuf<uint8_t>& d, const uint8_t* reusable, int32_t n_objects, hipStream_t stream) {
     d.ensure((size_t)std::max(n_objects, 1), "hipMalloc(reusable objects)");
     if (n_objects > 0)

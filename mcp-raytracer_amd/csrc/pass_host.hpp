@@ -1,7 +1,8 @@
-// What the frame passes' ABI units (api_denoise / api_reproject / api_temporal / api_focus.cpp)
-// share on the host: option fields, the region check and its copies, the guide and reusable-table
-// uploads, the open session's checks and passes, the filter's launch sequence and the common
-// head of the gather kernels' arguments.
+// What the frame passes' ABI units (api_denoise / api_reproject / api_temporal / api_focus.cpp and
+// the two *_spec_api.cpp) share on the host: option fields, the region check and its copies, the
+// guide and reusable-table uploads, the open session's checks and passes, the filter's launch
+// sequence, the common head of the gather kernels' arguments, and the reprojection's and the
+// accumulation's run, session and stand-alone bodies, each with an optional chain argument.
 #pragma once
 
 #include <functional>
@@ -60,6 +61,21 @@ struct RegionIo {
 // packed into b.gn / b.gp. Queued: the staging arrays may be reused by whatever is queued after.
 void upload_guides(DnBufs& b, const RegionIo& io, const float* normal, const float* position, const float* distance,
                    const int32_t* object);
+
+// A view's guide planes in a caller's arrays: the first-hit four and, through specular chains, the
+// chain four and the chain words (chain_normal null: none).
+struct HostGuides {
+    const float *normal, *position, *distance;
+    const int32_t* object;
+    const float *chain_normal, *chain_position, *chain_distance;
+    const int32_t *chain_object, *chain;
+};
+// Both views' planes of a stand-alone call: upload_guides of g through nb and of pg through pb and,
+// where a view has chain planes, of those through ns / ps, whose obj planes then take the chain
+// words (after their pack pass has read the chain objects). Allocates the four. Returns through
+// *ng / *pgd the device planes, the chain three null for a view without them. Queued.
+void upload_views(DnBufs& nb, DnBufs& ns, const RegionIo& io, const HostGuides& g, DnBufs& pb, DnBufs& ps,
+                  const RegionIo& pio, const HostGuides& pg, RsGuides* ng, RsGuides* pgd);
 
 // The caller's reusable table (n_objects >= 0 entries) into d, at least one byte. Queued.
 void upload_reusable(DevBuf<uint8_t>& d, const uint8_t* reusable, int32_t n_objects, hipStream_t stream);
@@ -173,16 +189,54 @@ struct TpOpts : GatherOpts {
 TpOpts tp_resolve(const rt_temporal_options* o, const std::string& who);
 // The hash a history keeps of its scene: the arrays the reprojection's same-scene check compares.
 uint64_t tp_scene_hash(const SceneBuild& b);
-// What follows the gather kernel of a call, which wrote out_col / out_var (weight -> b.dist()): the
-// caller's outputs - the optional variance-guided filter of out / Vout on the guides fgn / fgp,
-// else out itself - into b.rad() / b.u8 / b.var, and the length into b.nrm(). ev (or null): events
-// 2 and 3, recorded after the gather and after the filter. Queued.
-void tp_finish(DnBufs& b, const float4* fgn, const float4* fgp, const rt_region& r, const TpOpts& o, float4* out_col,
-               float* out_var, bool want_rad, bool want_u8, bool want_var, bool want_len, hipStream_t stream,
-               hipEvent_t* ev);
-// A call's outputs into the caller's arrays, then its one host sync.
-void tp_outputs(const DnBufs& b, const RegionIo& io, float* radiance, uint8_t* rgb, float* variance, float* length,
-                float* weight);
+// What a call through specular chains adds to the plain one: the new view's guide planes, the
+// history's (hg, read only when chain_history: it holds chain planes walked with the call's guide
+// options), the new view's centre, the through table, point_pixels resolved and the kind plane.
+struct TpChain {
+    RsGuides ng, hg;
+    bool chain_history;
+    const float* cn;
+    const uint8_t* d_through;
+    float point_pixels;
+    uint8_t* d_kind;
+};
+// The device side of a call: the gather and blend into out_col / out_var (weight -> b.dist(); ch:
+// through chains, kind -> ch->d_kind), then the caller's outputs - the optional variance-guided
+// filter of out / Vout on the new view's first-hit guides (ch: its chain guides), else out itself -
+// into b.rad() / b.u8 / b.var, and the length into b.nrm(). pr.width == 0: an empty history. ev (or
+// null): events 2 and 3, recorded after the gather and after the filter. Queued.
+void tp_run(DnBufs& b, const TpNew& nw, const rt_region& r, const TpHistory& hist, const RpView& view, const rt_region& pr,
+            const uint8_t* d_reusable, int n_objects, const TpOpts& o, float4* out_col, float* out_var, bool want_rad,
+            bool want_u8, bool want_var, bool want_len, hipStream_t stream, hipEvent_t* ev, const TpChain* ch = nullptr);
+// What the session call through chains adds: the guide options, the through mask and point_pixels
+// resolved, and the caller's kind plane.
+struct TpSessionChain {
+    rt_guide_options go;
+    int32_t through;
+    float point_pixels;
+    uint8_t* kind_out;
+};
+// rt_camera_progressive_accumulate[_specular] from session_with() on: the caller holds the history's
+// and the camera's locks and has resolved the options.
+void tp_session(rt_camera* cam, rt_history* h, const std::string& who, const TpOpts& o, int32_t commit, uint8_t* rgb,
+                float* radiance, float* variance_out, float* length_out, float* weight_out,
+                const TpSessionChain* sc = nullptr);
+// The arguments rt_temporal_accumulate[_specular] share, as the caller gave them and the entry
+// checked them; view (the new one), through and kind_out: through chains only, else null.
+struct TpCall {
+    int32_t width, height, samples, n_objects;
+    const rt_region *region, *prev_region;
+    const rt_view *view, *prev_view;
+    HostGuides g, pg;
+    const float *radiance, *variance, *prev_radiance, *prev_variance, *prev_length;
+    const int32_t* px_samples;
+    const uint8_t *reusable, *through;
+    float *radiance_out, *variance_out, *length_out, *weight_out;
+    uint8_t *rgb_out, *kind_out;
+};
+// A stand-alone call after its argument checks: the regions, the uploads, the run and the outputs.
+// point_pixels < 0: the plain call.
+void tp_explicit(const std::string& who, const TpCall& a, const TpOpts& o, float point_pixels = -1.0f);
 
 // ---- what the two specular ABI units share (reproject_spec_api.cpp) --------------------------------
 // The two fields rt_specular_reproject_options and rt_specular_temporal_options add to their base,

@@ -138,25 +138,18 @@ int rt_reproject_specular(int32_t width, int32_t height, const rt_region* region
         // (ns / ps: the chain guides' pairs, their obj planes the chain words, ns.u8 the kind plane)
         DnBufs nb, pb, ns, ps;
         DevBuf<uint8_t> d_reusable, d_through;
-        nb.ensure((size_t)io.n());
-        ns.ensure((size_t)io.n());
-        pb.ensure((size_t)pio.n());
-        ps.ensure((size_t)pio.n());
         upload_reusable(d_reusable, reusable, n_objects, stream);
         upload_reusable(d_through, through, n_objects, stream);
-        upload_guides(nb, io, normal, position, distance, object);
-        upload_guides(ns, io, chain_normal, chain_position, chain_distance, chain_object);
-        upload_guides(pb, pio, prev_normal, prev_position, prev_distance, prev_object);
-        upload_guides(ps, pio, prev_chain_normal, prev_chain_position, prev_chain_distance, prev_chain_object);
-        // (the guides are packed: the staging arrays now carry the chain words, the frames and the counts)
-        io.up(ns.obj, chain, sizeof(int32_t));
-        pio.up(ps.obj, prev_chain, sizeof(int32_t));
+        RsGuides ng, pg;
+        upload_views(nb, ns, io, {normal, position, distance, object, chain_normal, chain_position, chain_distance, chain_object, chain},
+                     pb, ps, pio, {prev_normal, prev_position, prev_distance, prev_object, prev_chain_normal, prev_chain_position,
+                                   prev_chain_distance, prev_chain_object, prev_chain}, &ng, &pg);
+        // (the guides are packed: the staging arrays now carry the frames and the counts)
         pio.up(pb.rad(), prev_radiance, 3 * sizeof(float));
         if (radiance) io.up(nb.rad(), radiance, 3 * sizeof(float));
         if (radiance && px_samples) io.up(nb.obj, px_samples, sizeof(int32_t));
         const RpNew nw{nb.gn, nb.gp, radiance ? nb.rad() : nullptr, radiance && px_samples ? nb.obj.p : nullptr,
                        io.r.width, 0, 0, (float)samples};
-        const RsGuides ng{nb.gn, nb.gp, ns.gn, ns.gp, ns.obj}, pg{pb.gn, pb.gp, ps.gn, ps.gp, ps.obj};
         const RpChain ch{ng, pg, view->center, d_through, o.point_pixels, ns.u8, kind_out != nullptr};
         rp_run(nb, pb, pv, io.r, pio.r, d_reusable, n_objects, o.base, nw, history_out || weight_out,
                radiance_out != nullptr, rgb_out != nullptr, stream, nullptr, &ch);

@@ -27,8 +27,8 @@ per-pixel history lengths and carries a variance the variance-guided filter cons
 surface they show. Vary `seed` per view.
 """
 from ._lib import RtError, build_id, device_count, progressive_blob_info, progressive_blob_variance
-from .camera import (Camera, History, ProgressiveRender, RenderStats, denoise, reproject, reproject_specular,
-                     rng_stream, temporal_accumulate, temporal_accumulate_specular)
+from .camera import Camera, History, ProgressiveRender, RenderStats, rng_stream
+from .passes import denoise, reproject, reproject_specular, temporal_accumulate, temporal_accumulate_specular
 from .raytracer import divide_into_regions, divideIntoRegions, generate_image_buffer, generateImageBuffer
 from .scenes import (create_camera_from_scene_data, createCameraFromSceneData, generate_scene,
                      generate_scene_data, generateScene, generateSceneData)

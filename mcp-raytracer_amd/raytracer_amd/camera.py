@@ -13,6 +13,10 @@ from dataclasses import dataclass, field
 from typing import Iterable, Optional, Sequence
 
 from . import _lib
+from .passes import (_as_frame, _denoise_out, _f32_frame, _f32_outs, _gather_options, _guide_options, _host_ptr,
+                     _region, _region_ptr, _reproject_frames, _reproject_options, _session_frame, _session_result,
+                     _temporal_options, _var_call, _var_out, _view_dict)
+from .passes import _c_view  # noqa: F401  (callers that imported it from this module still find it)
 
 RENDER_MODES = ("default", "bounces", "samples")
 
@@ -54,424 +58,6 @@ class RenderStats:
         return m
 
 
-def _region(region) -> _lib.RtRegion:
-    if isinstance(region, dict):
-        return _lib.RtRegion(int(region["x"]), int(region["y"]), int(region["width"]), int(region["height"]))
-    x, y, w, h = region
-    return _lib.RtRegion(int(x), int(y), int(w), int(h))
-
-
-def _host_ptr(buf, nbytes: int, what: str):
-    """Writable host pointer for a caller-owned buffer (bytearray / numpy / ctypes)."""
-    if buf is None:
-        return None, None
-    try:
-        import numpy as np  # noqa: F401
-        if hasattr(buf, "__array_interface__"):
-            arr = buf
-            if not arr.flags["C_CONTIGUOUS"] or not arr.flags["WRITEABLE"]:
-                raise ValueError(f"{what} must be a writable C-contiguous array")
-            if arr.nbytes < nbytes:
-                raise ValueError(f"{what} is too small: {arr.nbytes} < {nbytes} bytes")
-            return C.c_void_p(arr.ctypes.data), arr
-    except ImportError:  # pragma: no cover
-        pass
-    mv = memoryview(buf)
-    if mv.readonly or mv.nbytes < nbytes:
-        raise ValueError(f"{what} must be writable and hold at least {nbytes} bytes")
-    cbuf = (C.c_char * mv.nbytes).from_buffer(buf)
-    return C.cast(cbuf, C.c_void_p), cbuf
-
-
-def _denoise_options(levels, sigma_color, sigma_plane) -> _lib.RtDenoiseOptions:
-    """rt_denoise_options (a zero field = the default; the library validates the rest)."""
-    return _lib.RtDenoiseOptions(int(levels), float(sigma_color), float(sigma_plane))
-
-
-def _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane):
-    """Which filter a denoise call runs. Without `variance`: (False, rt_denoise_options) - the
-    colour edge-stop, sigma_color 0.5 unless given. With it: (True, rt_denoise_var_options)."""
-    if variance is None or variance is False:
-        if variance_out is not None:
-            raise ValueError("variance_out needs variance=")
-        return False, _denoise_options(levels, 0.5 if sigma_color is None else sigma_color, sigma_plane)
-    if sigma_color is not None:
-        raise ValueError("sigma_color belongs to the colour edge-stop: pass either sigma_color or variance=, not both")
-    return True, _lib.RtDenoiseVarOptions(int(levels), float(sigma_variance), float(sigma_plane))
-
-
-def _guide_options(guides) -> _lib.RtGuideOptions:
-    """rt_guide_options of a `guides=` keyword: "first_hit", "specular" (max_bounces 8, max_fuzz 0)
-    or a dict of max_bounces / max_fuzz for the specular walk (the library validates the values)."""
-    if isinstance(guides, str) and guides == "first_hit":
-        return _lib.RtGuideOptions(_lib.GUIDES_FIRST_HIT, 8, 0.0)
-    if isinstance(guides, str) and guides == "specular":
-        guides = {}
-    if not isinstance(guides, dict) or set(guides) - {"max_bounces", "max_fuzz"}:
-        raise ValueError('guides must be "first_hit", "specular" or a dict of max_bounces / max_fuzz')
-    return _lib.RtGuideOptions(_lib.GUIDES_SPECULAR, int(guides.get("max_bounces", 8)), float(guides.get("max_fuzz", 0.0)))
-
-
-def _var_out(variance_out, shape):
-    """Pointer of the optional caller-owned (H, W) float32 array the filtered variance goes to."""
-    import numpy as np
-    if variance_out is None:
-        return None
-    if (not isinstance(variance_out, np.ndarray) or variance_out.dtype != np.float32
-            or not variance_out.flags["C_CONTIGUOUS"] or not variance_out.flags["WRITEABLE"]
-            or variance_out.size != shape[0] * shape[1]):
-        raise ValueError("variance_out must be a writable C-contiguous float32 array of H*W values")
-    return variance_out.ctypes.data
-
-
-def _f32_frame(a, shape, what: str):
-    """`a` as a C-contiguous float32 / int32 array of `shape` (no copy when it already is)."""
-    import numpy as np
-    dtype = np.int32 if what == "object" else np.float32
-    arr = np.ascontiguousarray(a, dtype=dtype)
-    if arr.size != int(np.prod(shape)):
-        raise ValueError(f"{what} must hold {'x'.join(str(v) for v in shape)} values, not {arr.size}")
-    return arr.reshape(shape)
-
-
-def _denoise_out(src, out):
-    """The array a filter call writes: `out` (which may be the input itself) or a copy of the
-    input, so the pixels outside the region come back unchanged."""
-    import numpy as np
-    if out is None:
-        return np.array(src, dtype=np.float32, copy=True)
-    if (not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]
-            or not out.flags["WRITEABLE"] or out.size != src.size):
-        raise ValueError("out must be a writable C-contiguous float32 array of the radiance's size")
-    return out
-
-
-def denoise(radiance, normal, position, distance, object, region=None, *, levels=4, sigma_color=None,
-            sigma_plane=0.01, rgb=None, out=None, variance=None, sigma_variance=2.0, variance_out=None, chain=None):
-    """rt_denoise: the guided edge-avoiding a-trous filter of a frame with explicit guides (as
-    Camera.render_guides returns them), no camera. radiance / normal / position: float32
-    (H, W, 3); distance float32, object int32: (H, W). Returns the filtered radiance (H, W, 3) -
-    a new array, or `out` (which may be `radiance` itself); only the region is filtered. `rgb`
-    (optional caller-owned u8 H*W*3) receives the region's u8. Equals tests/denoise_ref.py in
-    every bit. sigma_color defaults to 0.5.
-
-    `variance` (float32 (H, W): the variance of each pixel's mean illuminance, as
-    ProgressiveRender.variance returns it) selects the variance-guided filter
-    (rt_denoise_variance, tests/denoise_var_ref.py) with `sigma_variance` in place of
-    sigma_color; `variance_out` (optional float32 (H, W)) then receives the region's filtered
-    variance. Passing sigma_color together with variance raises ValueError. `chain` is accepted
-    and ignored, so denoise(radiance, **cam.render_guides(through_specular=True)) works."""
-    import numpy as np
-    rad = np.asarray(radiance)
-    if rad.ndim != 3 or rad.shape[2] != 3:
-        raise ValueError("radiance must have shape (H, W, 3)")
-    H, W = rad.shape[:2]
-    rad = _f32_frame(rad, (H, W, 3), "radiance")
-    nrm = _f32_frame(normal, (H, W, 3), "normal")
-    pos = _f32_frame(position, (H, W, 3), "position")
-    dist = _f32_frame(distance, (H, W), "distance")
-    obj = _f32_frame(object, (H, W), "object")
-    res = _denoise_out(rad, out)
-    uptr, _k = _host_ptr(rgb, H * W * 3, "rgb")
-    reg = None if region is None else _region(region)
-    guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
-    rptr = C.byref(reg) if reg is not None else None
-    if guided:
-        var = _f32_frame(variance, (H, W), "variance")
-        _lib.check(_lib.load().rt_denoise_variance(W, H, rptr, C.byref(opts), rad.ctypes.data, var.ctypes.data,
-                                                   nrm.ctypes.data, pos.ctypes.data, dist.ctypes.data, obj.ctypes.data,
-                                                   res.ctypes.data, _var_out(variance_out, (H, W)), uptr))
-    else:
-        _lib.check(_lib.load().rt_denoise(W, H, rptr, C.byref(opts), rad.ctypes.data, nrm.ctypes.data, pos.ctypes.data,
-                                          dist.ctypes.data, obj.ctypes.data, res.ctypes.data, uptr))
-    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
-
-
-def _reproject_options(normal_min, sigma_plane, min_weight, history_samples) -> _lib.RtReprojectOptions:
-    """rt_reproject_options (a zero field = the default; the library validates the rest)."""
-    return _lib.RtReprojectOptions(float(normal_min), float(sigma_plane), float(min_weight), float(history_samples))
-
-
-def _out_array(a, dtype, shape, what: str):
-    """Pointer of an optional caller-owned output array of `shape` (any shape of that size)."""
-    import numpy as np
-    if a is None:
-        return None
-    if (not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]
-            or a.size != int(np.prod(shape))):
-        raise ValueError(f"{what} must be a writable C-contiguous {np.dtype(dtype).name} array of "
-                         f"{'x'.join(str(v) for v in shape)} values")
-    return a.ctypes.data
-
-
-def _reproject_frames(H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out):
-    """The new frame's side of a reproject call: (fresh radiance or None, its pointer, px_samples
-    pointer, scalar samples, blend array, its pointer, rgb pointer, history array, its pointer,
-    weight pointer, keep-alive). Without `radiance` there is no blend: out / rgb raise."""
-    import numpy as np
-    if radiance is None and (out is not None or rgb is not None or px_samples is not None):
-        raise ValueError("out, rgb and px_samples need radiance=")
-    rad = None if radiance is None else _f32_frame(radiance, (H, W, 3), "radiance")
-    pxs = None if px_samples is None else np.ascontiguousarray(px_samples, dtype=np.int32)
-    if pxs is not None and pxs.size != H * W:
-        raise ValueError(f"px_samples must hold {H}x{W} values, not {pxs.size}")
-    res = None if rad is None else _denoise_out(rad, out)
-    hist = np.zeros((H, W, 3), np.float32) if history_out is None and rad is None else history_out
-    uptr, keep = _host_ptr(rgb, H * W * 3, "rgb")
-    return (rad, None if rad is None else rad.ctypes.data, None if pxs is None else pxs.ctypes.data,
-            0 if samples is None else int(samples), res, None if res is None else res.ctypes.data, uptr, hist,
-            _out_array(hist, np.float32, (H, W, 3), "history_out"),
-            _out_array(weight_out, np.float32, (H, W), "weight_out"), (pxs, keep))
-
-
-def reproject(prev_radiance, prev_view, prev_guides, *, normal, position, distance, object, reusable, region=None,
-              prev_region=None, radiance=None, px_samples=None, samples=None, rgb=None, out=None, history_out=None,
-              weight_out=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0):
-    """rt_reproject: a previous view's frame reprojected into a new view, explicit buffers, no
-    camera. prev_radiance float32 (Hp, Wp, 3), prev_view as Camera.view() and prev_guides as
-    Camera.render_guides() of the previous camera; normal / position / distance / object: the new
-    view's guides (pass **cam.render_guides()); reusable: uint8 per object, as
-    Camera.reusable_objects(). With a fresh `radiance` (float32 (H, W, 3)) and its sample counts
-    (`px_samples` int32 (H, W), or one scalar `samples`) returns the blend (H, W, 3) - a new array,
-    or `out` - and `rgb` (optional u8 H*W*3) receives its u8; without, returns the history.
-    `history_out` (float32 (H, W, 3)) and `weight_out` (float32 (H, W)) are optional; only the
-    region is written. Equals tests/reproject_ref.py in every bit."""
-    import numpy as np
-    obj = np.asarray(object)
-    if obj.ndim != 2:
-        raise ValueError("object must have shape (H, W)")
-    H, W = obj.shape
-    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
-    view = _lib.RtView()
-    for k in ("center", "pixel00", "du", "dv"):
-        getattr(view, k)[:] = [float(v) for v in np.asarray(prev_view[k], dtype=np.float32)]
-    view.width, view.height = Wp, Hp
-    g = [_f32_frame(normal, (H, W, 3), "normal"), _f32_frame(position, (H, W, 3), "position"),
-         _f32_frame(distance, (H, W), "distance"), _f32_frame(obj, (H, W), "object")]
-    pg = [_f32_frame(prev_guides["normal"], (Hp, Wp, 3), "normal"),
-          _f32_frame(prev_guides["position"], (Hp, Wp, 3), "position"),
-          _f32_frame(prev_guides["distance"], (Hp, Wp), "distance"),
-          _f32_frame(prev_guides["object"], (Hp, Wp), "object")]
-    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
-    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
-    rad, radp, pxsp, ns, res, resp, uptr, hist, histp, wptr, _keep = _reproject_frames(
-        H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
-    reg = None if region is None else _region(region)
-    preg = None if prev_region is None else _region(prev_region)
-    opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
-    _lib.check(_lib.load().rt_reproject(
-        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], C.byref(view),
-        C.byref(preg) if preg is not None else None, prad.ctypes.data, *[a.ctypes.data for a in pg],
-        reus.ctypes.data if reus.size else None, int(reus.size), C.byref(opts), radp, pxsp, ns, histp, wptr, resp, uptr))
-    if res is None:
-        return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
-    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
-
-
-def _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, through):
-    """rt_specular_reproject_options (a zero field = the default; the library validates the rest)."""
-    return _lib.RtSpecularReprojectOptions(_reproject_options(normal_min, sigma_plane, min_weight, history_samples),
-                                           float(point_pixels), int(through))
-
-
-def _kind_out(kind, shape):
-    """Pointer of the optional caller-owned (H, W) uint8 array the kind plane goes to."""
-    import numpy as np
-    return _out_array(kind, np.uint8, shape, "kind")
-
-
-def _c_view(view) -> _lib.RtView:
-    import numpy as np
-    v = _lib.RtView()
-    for k in ("center", "pixel00", "du", "dv"):
-        getattr(v, k)[:] = [float(x) for x in np.asarray(view[k], dtype=np.float32)]
-    v.width, v.height = int(view["width"]), int(view["height"])
-    return v
-
-
-def reproject_specular(prev_radiance, prev_view, prev_first, prev_chain, view, first, chain, reusable, through, *,
-                       region=None, prev_region=None, radiance=None, px_samples=None, samples=None, rgb=None, out=None,
-                       history_out=None, weight_out=None, kind=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25,
-                       history_samples=32.0, point_pixels=4.0):
-    """rt_reproject_specular: reproject() through specular chains, explicit buffers, no camera.
-    first / prev_first: the new and the previous view's first-hit guides as Camera.render_guides()
-    returns them; chain / prev_chain: their guides through the chain, render_guides(
-    through_specular=True) of one max_bounces / max_fuzz (with "chain"); view: the new camera's
-    Camera.view(); reusable / through: uint8 per object, as Camera.reusable_objects() and
-    Camera.through_objects(). A pixel whose chain has length 0 is reproject()'s; a pixel that shows a
-    lambert or light surface through a chain finds its history at the chain's virtual point. `kind`
-    (optional uint8 (H, W)) receives 0 no history, 1 first hit, 2 chain. Everything else as
-    reproject(). Equals tests/specular_reproject_ref.py in every bit."""
-    import numpy as np
-    obj = np.asarray(first["object"])
-    if obj.ndim != 2:
-        raise ValueError("object must have shape (H, W)")
-    H, W = obj.shape
-    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
-
-    def planes(g, h, w, with_chain):
-        a = [_f32_frame(g["normal"], (h, w, 3), "normal"), _f32_frame(g["position"], (h, w, 3), "position"),
-             _f32_frame(g["distance"], (h, w), "distance"), _f32_frame(g["object"], (h, w), "object")]
-        if with_chain:
-            a.append(_f32_frame(g["chain"], (h, w), "object"))
-        return a
-    g = planes(first, H, W, False) + planes(chain, H, W, True)
-    pg = planes(prev_first, Hp, Wp, False) + planes(prev_chain, Hp, Wp, True)
-    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
-    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
-    thr = np.ascontiguousarray(through, dtype=np.uint8).ravel()
-    if thr.size != reus.size:
-        raise ValueError("reusable and through must hold one entry per object")
-    rad, radp, pxsp, ns, res, resp, uptr, hist, histp, wptr, _keep = _reproject_frames(
-        H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
-    reg = None if region is None else _region(region)
-    preg = None if prev_region is None else _region(prev_region)
-    opts = _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, 0)
-    v, pv = _c_view(view), _c_view(prev_view)
-    _lib.check(_lib.load().rt_reproject_specular(
-        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], C.byref(v), C.byref(pv),
-        C.byref(preg) if preg is not None else None, prad.ctypes.data, *[a.ctypes.data for a in pg],
-        reus.ctypes.data if reus.size else None, thr.ctypes.data if thr.size else None, int(reus.size), C.byref(opts),
-        radp, pxsp, ns, histp, wptr, resp, uptr, _kind_out(kind, (H, W))))
-    if res is None:
-        return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
-    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
-
-
-def _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance):
-    """rt_temporal_options (a zero field = the default; the library validates the rest)."""
-    return _lib.RtTemporalOptions(float(normal_min), float(sigma_plane), float(min_weight), float(max_history),
-                                  int(filter_levels), float(sigma_variance))
-
-
-def temporal_accumulate(prev_radiance, prev_variance, prev_length, prev_view, prev_guides, *, normal, position, distance,
-                        object, reusable, radiance, variance, px_samples=None, samples=None, region=None,
-                        prev_region=None, rgb=None, out=None, variance_out=None, length_out=None, weight_out=None,
-                        filter_levels=0, sigma_variance=2.0, normal_min=0.9, sigma_plane=0.01, min_weight=0.25,
-                        max_history=256.0):
-    """rt_temporal_accumulate: one accumulation step with explicit buffers, no camera and no
-    History. prev_radiance float32 (Hp, Wp, 3), prev_variance / prev_length float32 (Hp, Wp),
-    prev_view as Camera.view() and prev_guides as Camera.render_guides() of the previous view;
-    normal / position / distance / object: the new view's guides; reusable: uint8 per object;
-    radiance float32 (H, W, 3), variance float32 (H, W) and the sample counts (`px_samples` int32
-    (H, W), or one scalar `samples`) of the fresh frame. Returns the accumulated radiance (H, W, 3)
-    - `out`, or a new array that holds the fresh frame outside the region - filtered by the
-    variance-guided filter when filter_levels > 0; `rgb`, `variance_out`, `length_out` and
-    `weight_out` are optional; only the region is written. Equals tests/temporal_ref.py in every
-    bit. Views must be rendered with different seeds."""
-    import numpy as np
-    obj = np.asarray(object)
-    if obj.ndim != 2:
-        raise ValueError("object must have shape (H, W)")
-    H, W = obj.shape
-    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
-    view = _lib.RtView()
-    for k in ("center", "pixel00", "du", "dv"):
-        getattr(view, k)[:] = [float(v) for v in np.asarray(prev_view[k], dtype=np.float32)]
-    view.width, view.height = Wp, Hp
-    g = [_f32_frame(normal, (H, W, 3), "normal"), _f32_frame(position, (H, W, 3), "position"),
-         _f32_frame(distance, (H, W), "distance"), _f32_frame(obj, (H, W), "object")]
-    pg = [_f32_frame(prev_guides["normal"], (Hp, Wp, 3), "normal"),
-          _f32_frame(prev_guides["position"], (Hp, Wp, 3), "position"),
-          _f32_frame(prev_guides["distance"], (Hp, Wp), "distance"),
-          _f32_frame(prev_guides["object"], (Hp, Wp), "object")]
-    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
-    pvar = _f32_frame(prev_variance, (Hp, Wp), "prev_variance")
-    plen = _f32_frame(prev_length, (Hp, Wp), "prev_length")
-    rad = _f32_frame(radiance, (H, W, 3), "radiance")
-    var = _f32_frame(variance, (H, W), "variance")
-    pxs = None if px_samples is None else np.ascontiguousarray(px_samples, dtype=np.int32)
-    if pxs is not None and pxs.size != H * W:
-        raise ValueError(f"px_samples must hold {H}x{W} values, not {pxs.size}")
-    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
-    res = _denoise_out(rad, out)
-    uptr, _keep = _host_ptr(rgb, H * W * 3, "rgb")
-    reg = None if region is None else _region(region)
-    preg = None if prev_region is None else _region(prev_region)
-    opts = _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance)
-    _lib.check(_lib.load().rt_temporal_accumulate(
-        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], rad.ctypes.data,
-        None if pxs is None else pxs.ctypes.data, 0 if samples is None else int(samples), var.ctypes.data, C.byref(view),
-        C.byref(preg) if preg is not None else None, *[a.ctypes.data for a in pg], prad.ctypes.data, pvar.ctypes.data,
-        plen.ctypes.data, reus.ctypes.data if reus.size else None, int(reus.size), C.byref(opts), res.ctypes.data,
-        _out_array(variance_out, np.float32, (H, W), "variance_out"),
-        _out_array(length_out, np.float32, (H, W), "length_out"),
-        _out_array(weight_out, np.float32, (H, W), "weight_out"), uptr))
-    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
-
-
-def _specular_temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance,
-                               point_pixels, through):
-    """rt_specular_temporal_options (a zero field = the default; the library validates the rest)."""
-    return _lib.RtSpecularTemporalOptions(
-        _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance),
-        float(point_pixels), int(through))
-
-
-def temporal_accumulate_specular(prev_radiance, prev_variance, prev_length, prev_view, prev_first, prev_chain, view, first,
-                                 chain, reusable, through, *, radiance, variance, px_samples=None, samples=None,
-                                 region=None, prev_region=None, rgb=None, out=None, variance_out=None, length_out=None,
-                                 weight_out=None, kind=None, filter_levels=0, sigma_variance=2.0, normal_min=0.9,
-                                 sigma_plane=0.01, min_weight=0.25, max_history=256.0, point_pixels=4.0):
-    """rt_temporal_accumulate_specular: temporal_accumulate() through specular chains, explicit
-    buffers, no camera and no History. first / prev_first: the new and the previous view's first-hit
-    guides as Camera.render_guides() returns them; chain / prev_chain: their guides through the
-    chain, render_guides(through_specular=True) of one max_bounces / max_fuzz (with "chain");
-    prev_chain=None: the history holds no chain planes (every pixel behind a chain starts over);
-    view: the new camera's Camera.view(); reusable / through: uint8 per object, as
-    Camera.reusable_objects() and Camera.through_objects(). A pixel whose chain has length 0 is
-    temporal_accumulate()'s; a pixel that shows a lambert or light surface through a chain finds its
-    history - colour, length and variance - at the chain's virtual point. `kind` (optional uint8
-    (H, W)) receives 0 no history, 1 first hit, 2 chain. filter_levels > 0 filters with the chain
-    guides. Everything else as temporal_accumulate(). Equals tests/specular_temporal_ref.py in every
-    bit. Views must be rendered with different seeds."""
-    import numpy as np
-    obj = np.asarray(first["object"])
-    if obj.ndim != 2:
-        raise ValueError("object must have shape (H, W)")
-    H, W = obj.shape
-    Wp, Hp = int(prev_view["width"]), int(prev_view["height"])
-
-    def planes(g, h, w, with_chain):
-        a = [_f32_frame(g["normal"], (h, w, 3), "normal"), _f32_frame(g["position"], (h, w, 3), "position"),
-             _f32_frame(g["distance"], (h, w), "distance"), _f32_frame(g["object"], (h, w), "object")]
-        if with_chain:
-            a.append(_f32_frame(g["chain"], (h, w), "object"))
-        return a
-    g = planes(first, H, W, False) + planes(chain, H, W, True)
-    pg = planes(prev_first, Hp, Wp, False)
-    pcg = planes(prev_chain, Hp, Wp, True) if prev_chain is not None else None
-    prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
-    pvar = _f32_frame(prev_variance, (Hp, Wp), "prev_variance")
-    plen = _f32_frame(prev_length, (Hp, Wp), "prev_length")
-    rad = _f32_frame(radiance, (H, W, 3), "radiance")
-    var = _f32_frame(variance, (H, W), "variance")
-    pxs = None if px_samples is None else np.ascontiguousarray(px_samples, dtype=np.int32)
-    if pxs is not None and pxs.size != H * W:
-        raise ValueError(f"px_samples must hold {H}x{W} values, not {pxs.size}")
-    reus = np.ascontiguousarray(reusable, dtype=np.uint8).ravel()
-    thr = np.ascontiguousarray(through, dtype=np.uint8).ravel()
-    if thr.size != reus.size:
-        raise ValueError("reusable and through must hold one entry per object")
-    res = _denoise_out(rad, out)
-    uptr, _keep = _host_ptr(rgb, H * W * 3, "rgb")
-    reg = None if region is None else _region(region)
-    preg = None if prev_region is None else _region(prev_region)
-    opts = _specular_temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance,
-                                      point_pixels, 0)
-    v, pv = _c_view(view), _c_view(prev_view)
-    _lib.check(_lib.load().rt_temporal_accumulate_specular(
-        W, H, C.byref(reg) if reg is not None else None, *[a.ctypes.data for a in g], C.byref(v), rad.ctypes.data,
-        None if pxs is None else pxs.ctypes.data, 0 if samples is None else int(samples), var.ctypes.data, C.byref(pv),
-        C.byref(preg) if preg is not None else None, *[a.ctypes.data for a in pg],
-        *([a.ctypes.data for a in pcg] if pcg is not None else [None] * 5), prad.ctypes.data, pvar.ctypes.data,
-        plen.ctypes.data, reus.ctypes.data if reus.size else None, thr.ctypes.data if thr.size else None, int(reus.size),
-        C.byref(opts), res.ctypes.data, _out_array(variance_out, np.float32, (H, W), "variance_out"),
-        _out_array(length_out, np.float32, (H, W), "length_out"),
-        _out_array(weight_out, np.float32, (H, W), "weight_out"), uptr, _kind_out(kind, (H, W))))
-    return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
-
-
 class History:
     """A view history (rt_history_*): per pixel the accumulated radiance, the effective number of
     samples behind it and the variance of the accumulated mean's illuminance, kept on the device
@@ -494,15 +80,12 @@ class History:
     def info(self) -> dict:
         """rt_history_get_info: {"width", "height", "region", "views", "device", "scene_hash",
         "bytes", "view"} of the last committed view (views 0, device -1: empty)."""
-        import numpy as np
         i = _lib.RtHistoryInfo()
         _lib.check(self._lib.rt_history_get_info(self._handle(), C.byref(i)))
-        view = {k: np.array(list(getattr(i.view, k)), dtype=np.float32) for k in ("center", "pixel00", "du", "dv")}
-        view.update(width=int(i.view.width), height=int(i.view.height))
         return {"width": int(i.width), "height": int(i.height),
                 "region": (int(i.region.x), int(i.region.y), int(i.region.width), int(i.region.height)),
                 "views": int(i.views), "device": int(i.device), "scene_hash": int(i.scene_hash), "bytes": int(i.bytes),
-                "view": view}
+                "view": _view_dict(i.view)}
 
     @property
     def views(self) -> int:
@@ -775,8 +358,7 @@ class Camera:
         """Open a progressive session over `region` (default: the whole image) at zero
         samples (rt_camera_progressive_begin). A camera holds one session: opening
         another drops the first."""
-        reg = None if region is None else _region(region)
-        _lib.check(self._lib.rt_camera_progressive_begin(self._h, C.byref(reg) if reg is not None else None))
+        _lib.check(self._lib.rt_camera_progressive_begin(self._h, _region_ptr(region)))
         return ProgressiveRender(self)
 
     def resume(self, blob: bytes) -> "ProgressiveRender":
@@ -805,8 +387,7 @@ class Camera:
         H, W = self.image_height, self.image_width
         g = {"normal": np.zeros((H, W, 3), np.float32), "position": np.zeros((H, W, 3), np.float32),
              "distance": np.zeros((H, W), np.float32), "object": np.full((H, W), -1, np.int32)}
-        reg = None if region is None else _region(region)
-        rptr = C.byref(reg) if reg is not None else None
+        rptr = _region_ptr(region)
         if through_specular:
             g["chain"] = np.zeros((H, W), np.int32)
             opts = _lib.RtGuideOptions(_lib.GUIDES_SPECULAR, int(max_bounces), float(max_fuzz))
@@ -839,9 +420,8 @@ class Camera:
         rad = _f32_frame(radiance, (H, W, 3), "radiance")
         res = _denoise_out(rad, out)
         uptr, _k = _host_ptr(rgb, self.byte_length, "rgb")
-        reg = None if region is None else _region(region)
+        rptr = _region_ptr(region)
         guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
-        rptr = C.byref(reg) if reg is not None else None
         if guided:
             var = _f32_frame(variance, (H, W), "variance")
             _lib.check(self._lib.rt_camera_denoise_variance(self._h, rptr, C.byref(opts), rad.ctypes.data,
@@ -850,7 +430,7 @@ class Camera:
         else:
             _lib.check(self._lib.rt_camera_denoise(self._h, rptr, C.byref(opts), rad.ctypes.data, res.ctypes.data,
                                                    uptr))
-        return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+        return _as_frame(res, H, W)
 
     def denoise_times(self) -> dict:
         """Device time of the last denoise / ProgressiveRender.denoised call, from HIP events
@@ -866,12 +446,9 @@ class Camera:
     def view(self) -> dict:
         """The camera's view (rt_camera_get_view): {"center", "pixel00", "du", "dv": float32 (3,),
         "width", "height"} - the fp32 vectors the guide pass builds its rays from."""
-        import numpy as np
         v = _lib.RtView()
         _lib.check(self._lib.rt_camera_get_view(self._h, C.byref(v)))
-        d = {k: np.array(list(getattr(v, k)), dtype=np.float32) for k in ("center", "pixel00", "du", "dv")}
-        d.update(width=int(v.width), height=int(v.height))
-        return d
+        return _view_dict(v)
 
     def reusable_objects(self):
         """rt_camera_reusable_objects: uint8 per SceneData.objects entry, 1 where the object's
@@ -912,29 +489,18 @@ class Camera:
         receives 0 no history, 1 first hit, 2 chain. Equals reproject_specular() on both cameras'
         guides. Without `guides=` the three keywords must be left alone."""
         H, W = self.image_height, self.image_width
-        Hp, Wp = prev_cam.image_height, prev_cam.image_width
-        prad = _f32_frame(prev_radiance, (Hp, Wp, 3), "prev_radiance")
-        rad, radp, pxsp, ns, res, resp, uptr, hist, histp, wptr, _keep = _reproject_frames(
-            H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
-        reg = None if region is None else _region(region)
-        preg = None if prev_region is None else _region(prev_region)
-        rptr = C.byref(reg) if reg is not None else None
-        pptr = C.byref(preg) if preg is not None else None
-        if guides is None:
-            if kind is not None or point_pixels != 4.0 or through != 15:
-                raise ValueError("kind, point_pixels and through need guides=")
-            opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+        prad = _f32_frame(prev_radiance, (prev_cam.image_height, prev_cam.image_width, 3), "prev_radiance")
+        args, res, _keep = _reproject_frames(H, W, radiance, px_samples, samples, rgb, out, history_out, weight_out)
+        rptr, pptr = _region_ptr(region), _region_ptr(prev_region)
+        go, opts, *kptr = _gather_options(guides, _reproject_options(normal_min, sigma_plane, min_weight, history_samples),
+                                          _lib.RtSpecularReprojectOptions, point_pixels, through, kind, (H, W))
+        if go is None:
             _lib.check(self._lib.rt_camera_reproject(self._h, rptr, prev_cam._h, pptr, C.byref(opts), prad.ctypes.data,
-                                                     radp, pxsp, ns, histp, wptr, resp, uptr))
+                                                     *args))
         else:
-            go = _guide_options(guides)
-            opts = _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, through)
             _lib.check(self._lib.rt_camera_reproject_specular(self._h, rptr, prev_cam._h, pptr, C.byref(go),
-                                                              C.byref(opts), prad.ctypes.data, radp, pxsp, ns, histp,
-                                                              wptr, resp, uptr, _kind_out(kind, (H, W))))
-        if res is None:
-            return hist if hist.shape == (H, W, 3) else hist.reshape(H, W, 3)
-        return res if res.shape == (H, W, 3) else res.reshape(H, W, 3)
+                                                              C.byref(opts), prad.ctypes.data, *args, *kptr))
+        return res
 
     def reproject_times(self) -> dict:
         """Device time of the last reproject / ProgressiveRender.reprojected call, from HIP events
@@ -1108,23 +674,16 @@ class ProgressiveRender:
         recomputes them when max_bounces or max_fuzz change."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
-        import numpy as np
         cam = self._cam
         cam._set_denoise_guides(guides)
-        if radiance is None:
-            radiance = np.zeros((cam.image_height, cam.image_width, 3), np.float32)
-        ptr, _k0 = _host_ptr(buffer, cam.byte_length, "buffer")
-        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
+        ptr, rptr, radiance, _keep = _session_frame(cam, buffer, radiance, "buffer")
         guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
         if guided:
             vptr = _var_out(variance_out, (cam.image_height, cam.image_width))
             _lib.check(cam._lib.rt_camera_progressive_denoise_variance(cam._h, C.byref(opts), ptr, rptr, vptr))
         else:
             _lib.check(cam._lib.rt_camera_progressive_denoise(cam._h, C.byref(opts), ptr, rptr))
-        shape = (cam.image_height, cam.image_width, 3)
-        if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
-            return radiance.reshape(shape)
-        return radiance
+        return _session_result(cam, radiance)
 
     def reprojected(self, prev_cam: Camera, prev_radiance, rgb=None, radiance=None, weight_out=None, *,
                     prev_region=None, normal_min=0.9, sigma_plane=0.01, min_weight=0.25, history_samples=32.0,
@@ -1141,32 +700,21 @@ class ProgressiveRender:
         chain plane beside its first-hit ones; its state and checkpoint bytes are not touched."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
-        import numpy as np
         cam = self._cam
-        shape = (cam.image_height, cam.image_width, 3)
-        if radiance is None:
-            radiance = np.zeros(shape, np.float32)
+        H, W = cam.image_height, cam.image_width
         prad = _f32_frame(prev_radiance, (prev_cam.image_height, prev_cam.image_width, 3), "prev_radiance")
-        ptr, _k0 = _host_ptr(rgb, cam.byte_length, "rgb")
-        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
-        wptr = _out_array(weight_out, np.float32, shape[:2], "weight_out")
-        preg = None if prev_region is None else _region(prev_region)
-        pptr = C.byref(preg) if preg is not None else None
-        if guides is None:
-            if kind is not None or point_pixels != 4.0 or through != 15:
-                raise ValueError("kind, point_pixels and through need guides=")
-            opts = _reproject_options(normal_min, sigma_plane, min_weight, history_samples)
+        ptr, rptr, radiance, _keep = _session_frame(cam, rgb, radiance)
+        wptr, = _f32_outs(H, W, weight_out=weight_out)
+        pptr = _region_ptr(prev_region)
+        go, opts, *kptr = _gather_options(guides, _reproject_options(normal_min, sigma_plane, min_weight, history_samples),
+                                          _lib.RtSpecularReprojectOptions, point_pixels, through, kind, (H, W))
+        if go is None:
             _lib.check(cam._lib.rt_camera_progressive_reproject(cam._h, prev_cam._h, pptr, C.byref(opts),
                                                                 prad.ctypes.data, ptr, rptr, wptr))
         else:
-            go = _guide_options(guides)
-            opts = _specular_options(normal_min, sigma_plane, min_weight, history_samples, point_pixels, through)
             _lib.check(cam._lib.rt_camera_progressive_reproject_specular(
-                cam._h, prev_cam._h, pptr, C.byref(go), C.byref(opts), prad.ctypes.data, ptr, rptr, wptr,
-                _kind_out(kind, shape[:2])))
-        if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
-            return radiance.reshape(shape)
-        return radiance
+                cam._h, prev_cam._h, pptr, C.byref(go), C.byref(opts), prad.ctypes.data, ptr, rptr, wptr, *kptr))
+        return _session_result(cam, radiance)
 
     def accumulated(self, history: History, rgb=None, radiance=None, *, commit=True, variance_out=None,
                     length_out=None, weight_out=None, filter_levels=0, sigma_variance=2.0, normal_min=0.9,
@@ -1190,36 +738,24 @@ class ProgressiveRender:
         chain finds its history at the chain's virtual point, on the chain planes the history keeps
         of its view (History.chain_guides) - if a call with the same `guides` committed them; the
         filter then uses the chain guides. `point_pixels`, `through` and `kind` (uint8 (H, W): 0 no
-        history, 1 first hit, 2 chain) as in reprojected(); they need guides=. Plain and specular
+        history, 1 first hit, 2 chain) as in reprojected(), with `guides` only. Plain and specular
         calls mix freely on one history; the session's state and checkpoint bytes are not touched."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
-        import numpy as np
         cam = self._cam
-        shape = (cam.image_height, cam.image_width, 3)
-        if radiance is None:
-            radiance = np.zeros(shape, np.float32)
-        ptr, _k0 = _host_ptr(rgb, cam.byte_length, "rgb")
-        rptr, _k1 = _host_ptr(radiance, cam.byte_length * 4, "radiance")
-        outs = (_out_array(variance_out, np.float32, shape[:2], "variance_out"),
-                _out_array(length_out, np.float32, shape[:2], "length_out"),
-                _out_array(weight_out, np.float32, shape[:2], "weight_out"))
-        if guides is None:
-            if kind is not None or point_pixels != 4.0 or through != 15:
-                raise ValueError("kind, point_pixels and through need guides=")
-            opts = _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance)
+        H, W = cam.image_height, cam.image_width
+        ptr, rptr, radiance, _keep = _session_frame(cam, rgb, radiance)
+        outs = _f32_outs(H, W, variance_out=variance_out, length_out=length_out, weight_out=weight_out)
+        go, opts, *kptr = _gather_options(
+            guides, _temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels, sigma_variance),
+            _lib.RtSpecularTemporalOptions, point_pixels, through, kind, (H, W))
+        if go is None:
             _lib.check(cam._lib.rt_camera_progressive_accumulate(
                 cam._h, history._handle(), C.byref(opts), 1 if commit else 0, ptr, rptr, *outs))
         else:
-            go = _guide_options(guides)
-            opts = _specular_temporal_options(normal_min, sigma_plane, min_weight, max_history, filter_levels,
-                                              sigma_variance, point_pixels, through)
             _lib.check(cam._lib.rt_camera_progressive_accumulate_specular(
-                cam._h, history._handle(), C.byref(go), C.byref(opts), 1 if commit else 0, ptr, rptr, *outs,
-                _kind_out(kind, shape[:2])))
-        if isinstance(radiance, np.ndarray) and radiance.dtype == np.float32 and radiance.shape != shape:
-            return radiance.reshape(shape)
-        return radiance
+                cam._h, history._handle(), C.byref(go), C.byref(opts), 1 if commit else 0, ptr, rptr, *outs, *kptr))
+        return _session_result(cam, radiance)
 
     @property
     def info(self) -> dict:

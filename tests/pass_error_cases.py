@@ -1,6 +1,6 @@
 """The argument-error cases of the frame passes' C entries (filter, reprojection, accumulation,
-focused steps), at the raw ABI: one fault per row, plus rows with two faults that pin which error
-wins. tests/golden/make_pass_errors.py records (return code, rt_last_error) of every row;
+focused steps, and the reprojection and accumulation through specular chains), at the raw ABI: one
+fault per row, plus rows with two faults that pin which error wins. tests/golden/make_pass_errors.py records (return code, rt_last_error) of every row;
 tests/test_pass_errors.py replays them. Everything is a 16x16 Cornell camera (samples 4, depth 4)
 and 16x16 zero frames."""
 import ctypes as C
@@ -16,10 +16,16 @@ RO = {"width": 16, "samples": 4, "depth": 4}
 
 # parameter kinds - i: int32; region: rt_region* (None: NULL); Rt*: the options struct (None: NULL,
 # a dict: its fields over zeros - over rt_focus_options_default for the focus options); in: a
-# required input array; opt / out: an optional array (NULL); view: the previous rt_view; reuse: the
-# reusable table; cam / prev_cam / hist: handles.
+# required input array; opt / out: an optional array (NULL); optin: an optional input that is given
+# unless a row takes it away (the previous view's chain planes); view: an rt_view, the new or the
+# previous one; reuse: a per-object table (reusable, through); RtGuideOptions: rt_guide_options
+# (None: NULL, a dict: its fields over the specular walk's defaults); cam / prev_cam / hist: handles.
 _GUIDES = [(n, "in") for n in ("normal", "position", "distance", "object")]
 _PREV_GUIDES = [("prev_" + n, "in") for n in ("normal", "position", "distance", "object")]
+_CHAIN = [("chain_" + n, "in") for n in ("normal", "position", "distance", "object")] + [("chain", "in")]
+_PREV_CHAIN = [("prev_" + n, "in") for n, _ in _CHAIN]
+_PREV_CHAIN_OPT = [(n, "optin") for n, _ in _PREV_CHAIN]
+_SPEC_GO = ("guide_options", "RtGuideOptions")
 ENTRIES = {
     "rt_denoise": [("width", "i"), ("height", "i"), ("region", "region"), ("options", "RtDenoiseOptions"),
                    ("radiance", "in"), *_GUIDES, ("radiance_out", "out"), ("rgb_out", "out")],
@@ -60,16 +66,58 @@ ENTRIES = {
     "rt_camera_progressive_focus": [("cam", "cam"), ("n_samples", "i"), ("options", "RtFocusOptions"), ("score", "opt"),
                                     ("h", "opt_hist"), ("rgb", "out"), ("radiance", "out"), ("px_samples", "out"),
                                     ("px_bounces", "out"), ("selected_out", "out"), ("stats", "out"), ("info", "out")],
+    # through specular chains
+    "rt_reproject_specular": [("width", "i"), ("height", "i"), ("region", "region"), *_GUIDES, *_CHAIN, ("view", "view"),
+                              ("prev_view", "view"), ("prev_region", "region"), ("prev_radiance", "in"), *_PREV_GUIDES,
+                              *_PREV_CHAIN, ("reusable", "reuse"), ("through", "reuse"), ("n_objects", "i"),
+                              ("options", "RtSpecularReprojectOptions"), ("radiance", "opt"), ("px_samples", "opt"),
+                              ("samples", "i"), ("history_out", "out"), ("weight_out", "out"), ("radiance_out", "out"),
+                              ("rgb_out", "out"), ("kind_out", "out")],
+    "rt_camera_reproject_specular": [("cam", "cam"), ("region", "region"), ("prev_cam", "prev_cam"),
+                                     ("prev_region", "region"), _SPEC_GO, ("options", "RtSpecularReprojectOptions"),
+                                     ("prev_radiance", "in"), ("radiance", "opt"), ("px_samples", "opt"), ("samples", "i"),
+                                     ("history_out", "out"), ("weight_out", "out"), ("radiance_out", "out"),
+                                     ("rgb_out", "out"), ("kind_out", "out")],
+    "rt_camera_progressive_reproject_specular": [("cam", "cam"), ("prev_cam", "prev_cam"), ("prev_region", "region"),
+                                                 _SPEC_GO, ("options", "RtSpecularReprojectOptions"),
+                                                 ("prev_radiance", "in"), ("rgb", "out"), ("radiance", "out"),
+                                                 ("weight_out", "out"), ("kind_out", "out")],
+    "rt_temporal_accumulate_specular": [("width", "i"), ("height", "i"), ("region", "region"), *_GUIDES, *_CHAIN,
+                                        ("view", "view"), ("radiance", "in"), ("px_samples", "opt"), ("samples", "i"),
+                                        ("variance", "in"), ("prev_view", "view"), ("prev_region", "region"), *_PREV_GUIDES,
+                                        *_PREV_CHAIN_OPT, ("prev_radiance", "in"), ("prev_variance", "in"),
+                                        ("prev_length", "in"), ("reusable", "reuse"), ("through", "reuse"),
+                                        ("n_objects", "i"), ("options", "RtSpecularTemporalOptions"), ("radiance_out", "out"),
+                                        ("variance_out", "out"), ("length_out", "out"), ("weight_out", "out"),
+                                        ("rgb_out", "out"), ("kind_out", "out")],
+    "rt_camera_progressive_accumulate_specular": [("cam", "cam"), ("h", "hist"), _SPEC_GO,
+                                                  ("options", "RtSpecularTemporalOptions"), ("commit", "i"), ("rgb", "out"),
+                                                  ("radiance", "out"), ("variance_out", "out"), ("length_out", "out"),
+                                                  ("weight_out", "out"), ("kind_out", "out")],
 }
+SPECULAR = [e for e in ENTRIES if e.endswith("_specular")]
+# the previous view's chain planes partly given: the planes taken away
+PARTLY = {"no prev_chain_normal": ["prev_chain_normal"], "no prev_chain_position and distance":
+          ["prev_chain_position", "prev_chain_distance"], "no prev_chain": ["prev_chain"],
+          "prev_chain alone": [n for n, _ in _PREV_CHAIN[:4]]}
 _INT_DEFAULTS = {"width": 16, "height": 16, "n_objects": 1, "samples": 4, "commit": 1, "n_samples": 1}
 _REQUIRED = ("in", "view", "reuse", "cam", "prev_cam", "hist")
 FOCUS = "rt_camera_progressive_focus"
 
 
+def _option_fields(struct, prefix=""):
+    """(dotted field name, its bad values) of an options struct, nested structs (`base`) walked."""
+    for f, t in struct._fields_:
+        if isinstance(t, type) and issubclass(t, C.Structure):
+            yield from _option_fields(t, prefix + f + ".")
+        else:
+            yield prefix + f, list(BAD) if t is C.c_float else [-1, 16] if f == "through" else [-1, 9]
+
+
 def cases():
     """[(id, entry, overrides)]: overrides by parameter name - None: NULL; a 4-tuple: a region; a
-    dict: option fields (floats as BAD's keys); "w0": a previous view of width 0; "other": a camera
-    of another scene; "hist": a history; an int."""
+    dict: option fields (floats as BAD's keys, a nested struct's as "base.field"); "w0": a previous
+    view of width 0; "other": a camera of another scene; "hist": a history; an int."""
     from raytracer_amd import _lib
     out = []
 
@@ -83,9 +131,13 @@ def cases():
                 add(entry, f"no {n}", **{n: None})
         opts = dict(params)["options"] if "options" in names else None
         if opts and entry != FOCUS:
-            for f, t in getattr(_lib, opts)._fields_:
-                for v in (list(BAD) if t is C.c_float else [-1, 9]):
+            for f, bad in _option_fields(getattr(_lib, opts)):
+                for v in bad:
                     add(entry, f"{f}={v}", options={f: v})
+        if "guide_options" in names:
+            for f, v in (("mode", 7), ("max_bounces", 0), ("max_bounces", 65), ("max_fuzz", -1.0), ("max_fuzz", "nan")):
+                add(entry, f"guide_options {f}={v}", guide_options={f: v})
+            add(entry, "first-hit guide options", guide_options={"mode": 0})
         for key in ("region", "prev_region"):
             if key in names:
                 for r in EMPTY_REGIONS:
@@ -150,6 +202,47 @@ def cases():
     add(FOCUS, "history source without a history + min_score=-0.5", options={"source": 2, "min_score": "-0.5"})
     add(FOCUS, "map source without a map + max_pixels=-1", options={"source": 1, "max_pixels": -1})
     add(FOCUS, "empty history + no session", options={"source": 2}, h="hist")
+
+    # through specular chains ("no through" above is through NULL with n_objects 1)
+    e = "rt_temporal_accumulate_specular"
+    for label, gone in PARTLY.items():
+        add(e, f"partly given, {label}", **{n: None for n in gone})
+    add(e, "partly given, no prev_chain + samples=-1", prev_chain=None, samples=-1)
+    add(e, "partly given, no prev_chain + no prev_length", prev_chain=None, prev_length=None)
+    add(e, "partly given, no prev_chain + prev_view width 0", prev_chain=None, prev_view="w0")
+    add(e, "base.filter_levels=9 + through=16", options={"base.filter_levels": 9, "through": 16})
+    add(e, "no view + no chain", view=None, chain=None)
+    add("rt_reproject_specular", "no prev_chain + samples=-1", prev_chain=None, samples=-1)
+    add("rt_reproject_specular", "n_objects=-1 + no prev_radiance", n_objects=-1, prev_radiance=None)
+    add("rt_reproject_specular", "no view + no prev_view", view=None, prev_view=None)
+    for e in SPECULAR:
+        names = [n for n, _ in ENTRIES[e]]
+        add(e, "base.sigma_plane=-0.5 + point_pixels=nan", options={"base.sigma_plane": "-0.5", "point_pixels": "nan"})
+        add(e, "point_pixels=inf + through=-1", options={"point_pixels": "inf", "through": -1})
+        if "guide_options" in names:
+            add(e, "through=16 + guide_options mode=7", options={"through": 16}, guide_options={"mode": 7})
+            add(e, "base.min_weight=nan + first-hit guide options", options={"base.min_weight": "nan"},
+                guide_options={"mode": 0})
+            add(e, "guide_options max_bounces=65 + max_fuzz=nan", guide_options={"max_bounces": 65, "max_fuzz": "nan"})
+        for key in ("region", "prev_region"):
+            if key in names:
+                add(e, f"point_pixels=-0.5 + empty {key}", options={"point_pixels": "-0.5"}, **{key: EMPTY_REGIONS[0]})
+                if "guide_options" in names:
+                    add(e, f"guide_options max_fuzz=-1.0 + empty {key}", guide_options={"max_fuzz": -1.0},
+                        **{key: EMPTY_REGIONS[1]})
+        if "chain" in names:
+            add(e, "no chain + through=16", chain=None, options={"through": 16})
+            add(e, "no chain_object + base.normal_min=nan", chain_object=None, options={"base.normal_min": "nan"})
+            add(e, "no through + point_pixels=-0.5", through=None, options={"point_pixels": "-0.5"})
+        if "h" in names:
+            add(e, "no h + base.normal_min=nan", h=None, options={"base.normal_min": "nan"})
+            add(e, "no h + guide_options mode=7", h=None, guide_options={"mode": 7})
+        if "prev_cam" in names:
+            add(e, "through=16 + different scenes", options={"through": 16}, prev_cam="other")
+            add(e, "first-hit guide options + different scenes", guide_options={"mode": 0}, prev_cam="other")
+            add(e, "no prev_radiance + point_pixels=nan", prev_radiance=None, options={"point_pixels": "nan"})
+        if "samples" in names:
+            add(e, "samples=-1 + base.min_weight=inf", samples=-1, options={"base.min_weight": "inf"})
     assert len({c[0] for c in out}) == len(out)
     return out
 
@@ -187,14 +280,20 @@ class Env:
                     o = getattr(_lib, kind)()
                     if kind == "RtFocusOptions":
                         lib.rt_focus_options_default(C.byref(o))
+                    elif kind == "RtGuideOptions":
+                        o.mode, o.max_bounces = _lib.GUIDES_SPECULAR, 8
                     for f, x in v.items():
-                        setattr(o, f, BAD.get(x, x))
+                        *path, leaf = f.split(".")
+                        part = o
+                        for p in path:
+                            part = getattr(part, p)
+                        setattr(part, leaf, BAD.get(x, x))
                     keep.append(o)
                     a = C.byref(o)
             elif isinstance(v, np.ndarray):  # a caller's array, any array parameter
                 assert v.flags["C_CONTIGUOUS"]
                 a = v.ctypes.data
-            elif kind == "in":
+            elif kind in ("in", "optin"):
                 a = None if has else self.zeros.ctypes.data
             elif kind == "view":
                 a = None
@@ -216,7 +315,7 @@ class Env:
             elif kind == "prev_cam":
                 a = self.other._h if v == "other" else None if has else self.prev._h
             elif kind == "hist":
-                a = None if has else self.hist._h
+                a = self.hist._h if not has or v == "hist" else None
             else:  # opt, out, opt_hist
                 a = self.hist._h if v == "hist" else None
             args.append(a)
@@ -227,10 +326,13 @@ class Env:
 # ---- rows that need an open session (a GPU) ---------------------------------------------------------
 def session_cases():
     """[(id, env, entry, overrides)] - env "bounces": a mode-bounces camera, "radiance": the default
-    mode; both with a session at samples_done 1. h "hist": an empty history, "region": a history
-    committed by another camera's session over the region (0, 0, 8, 8)."""
+    mode; both with a session at samples_done 1; "two": the default mode at samples_done 2. h "hist":
+    an empty history, "region": a history committed by another camera's session over the region
+    (0, 0, 8, 8), "scene": a history committed by a camera of another scene."""
     two = {"levels": 9, "sigma_plane": "-0.5"}
     var, hsrc = {"source": 0}, {"source": 2}
+    acc, acs = "rt_camera_progressive_accumulate", "rt_camera_progressive_accumulate_specular"
+    rps = "rt_camera_progressive_reproject_specular"
     return [
         ("plain filter, bounces + levels=9: the mode", "bounces", "rt_camera_progressive_denoise", {"options": two}),
         ("variance-guided filter, bounces + levels=9: the options", "bounces", "rt_camera_progressive_denoise_variance",
@@ -243,26 +345,55 @@ def session_cases():
          {"options": {"sigma_plane": "nan"}, "prev_cam": "other"}),
         ("focus on an empty history", "radiance", FOCUS, {"options": hsrc, "h": "hist"}),
         ("focus on a history of another region", "radiance", FOCUS, {"options": hsrc, "h": "region"}),
+        # the session body the two accumulate entries share, and the entries through specular chains
+        ("accumulated on a history of another scene", "two", acc, {"h": "scene"}),
+        ("accumulated, filter_levels=9 + a history of another scene", "two", acc,
+         {"options": {"filter_levels": 9}, "h": "scene"}),
+        ("accumulated, bounces", "bounces", acc, {}),
+        ("specular accumulated at 1 sample", "radiance", acs, {}),
+        ("specular accumulated on a history of another scene", "two", acs, {"h": "scene"}),
+        ("specular accumulated without commit on a history of another scene", "two", acs, {"h": "scene", "commit": 0}),
+        ("specular accumulated, through=16 + a history of another scene", "two", acs,
+         {"options": {"through": 16}, "h": "scene"}),
+        ("specular accumulated, first-hit guide options + a history of another scene", "two", acs,
+         {"guide_options": {"mode": 0}, "h": "scene"}),
+        ("specular accumulated, bounces", "bounces", acs, {}),
+        ("specular accumulated, bounces + point_pixels=nan: the options", "bounces", acs,
+         {"options": {"point_pixels": "nan"}}),
+        ("specular accumulated at 1 sample + guide_options max_bounces=0: the options", "radiance", acs,
+         {"guide_options": {"max_bounces": 0}}),
+        ("specular reprojected, base.sigma_plane=nan + different scenes", "radiance", rps,
+         {"options": {"base.sigma_plane": "nan"}, "prev_cam": "other"}),
+        ("specular reprojected, different scenes", "radiance", rps, {"prev_cam": "other"}),
+        ("specular reprojected, first-hit guide options + different scenes", "radiance", rps,
+         {"guide_options": {"mode": 0}, "prev_cam": "other"}),
+        ("specular reprojected, empty prev_region + different scenes", "radiance", rps,
+         {"prev_region": EMPTY_REGIONS[0], "prev_cam": "other"}),
+        ("specular reprojected, bounces + through=16: the mode", "bounces", rps, {"options": {"through": 16}}),
     ]
 
 
 class SessionEnv:
-    """Env per camera mode with one step(1) done, and the history of another region."""
+    """Env per camera mode with one step(1) done ("two": step(2)), and the histories of another
+    region and of another scene."""
 
     def __init__(self, rt):
-        self.envs = {"radiance": Env(rt), "bounces": Env(rt, {**RO, "mode": "bounces"})}
+        self.envs = {"radiance": Env(rt), "bounces": Env(rt, {**RO, "mode": "bounces"}), "two": Env(rt)}
         self.sessions = [e.cam.progressive() for e in self.envs.values()]
-        for s in self.sessions:
-            s.step(1)
-        self.region_hist = rt.History()
+        for name, s in zip(self.envs, self.sessions):
+            s.step(2 if name == "two" else 1)
+        self.hists = {"region": rt.History(), "scene": rt.History()}
         with self.envs["radiance"].prev.progressive((0, 0, 8, 8)) as pr:
             pr.step(2)
-            pr.accumulated(self.region_hist)
+            pr.accumulated(self.hists["region"])
+        with self.envs["radiance"].other.progressive() as pr:
+            pr.step(2)
+            pr.accumulated(self.hists["scene"])
 
     def call(self, env, entry, ov):
         e = self.envs[env]
-        if ov.get("h") == "region":
-            keep, e.hist = e.hist, self.region_hist
+        if ov.get("h") in self.hists:
+            keep, e.hist = e.hist, self.hists[ov["h"]]
             try:
                 return e.call(entry, {**ov, "h": "hist"})
             finally:

@@ -14,7 +14,7 @@ from guide_walk_ref import guide_walk_ref  # noqa: E402
 from reproject_ref import moved_scene  # noqa: E402
 from specular_reproject_ref import (PREV_REGION, REGION, cornell_without_spheres, golden_scene,  # noqa: E402
                                     mirror_room, synthetic_pair, through_from_scene)
-from specular_temporal_ref import (GUIDE_KEYS, specular_temporal_ref, synthetic_history,  # noqa: E402
+from specular_temporal_ref import (GUIDE_KEYS, plain_history, specular_temporal_ref, synthetic_history,  # noqa: E402
                                    synthetic_variance)
 from temporal_ref import accumulate_ref  # noqa: E402
 
@@ -102,7 +102,7 @@ def test_explicit_buffers_on_the_synthetic_sequence(rt, gpu, opts, counts, level
 def _raw_explicit(rt, hist, s, var, region, prev_region, levels, outs):
     """The raw entry with the output pointers of `outs` only."""
     from raytracer_amd import _lib
-    from raytracer_amd.camera import _c_view, _region
+    from raytracer_amd.passes import _c_view, _region
     f32 = lambda a: np.ascontiguousarray(a, F)                                   # noqa: E731
     i32 = lambda a: np.ascontiguousarray(a, np.int32)                            # noqa: E731
     planes = lambda g, ch: ([f32(g["normal"]), f32(g["position"]), f32(g["distance"]), i32(g["object"])]   # noqa: E731
@@ -333,6 +333,55 @@ def test_commit_false_mixing_and_the_untouched_session(rt, gpu):
         assert (rgb_p == rgb_q).all() and bits_equal(rad_p, rad_q).all() and (pxs_p == pxs_q).all()
         assert (st_p.pixels, st_p.samples, st_p.bounces) == (st_q.pixels, st_q.samples, st_q.bounces)
         assert pr.save() == pq.save()
+
+
+def test_one_history_fed_by_plain_and_specular_calls_follows_both_restatements(rt, gpu, oracle):
+    """The session body the two accumulate entries share: one history over four views of the 16x16
+    mirror room - a plain commit, a specular commit, a specular commit=False, a plain commit - with
+    every output requested. Each call's outputs and the history's planes are the restatements' in
+    every bit; the chain planes are held after the specular commit only."""
+    sd, ro, go = mirror_room(), {"width": 16, "samples": 60, "depth": 8}, (8, 0.0)
+    ref_hist, views, sizes, held = None, 0, [], []
+    with rt.History() as history:
+        for k, (plain, commit) in enumerate([(True, True), (False, True), (False, False), (True, True)]):
+            cam = view_camera(rt, sd, ro, k)
+            H, W = cam.image_height, cam.image_width
+            assert (H, W) == (16, 16)
+            first, chain = oracle_planes(oracle, sd, ro, k, go)
+            reus, thr = cam.reusable_objects(), cam.through_objects(15, go[1])
+            with cam.progressive() as pr:
+                _step(cam, pr, 10)
+                _, rad, pxs, _ = _step(cam, pr, 10)
+                var = pr.variance()
+                if plain:
+                    want, committed = accumulate_ref(ref_hist and plain_history(ref_hist), cam.view(), first, rad, var, reus,
+                                                     px_samples=pxs)
+                else:
+                    want = specular_temporal_ref(ref_hist, cam.view(), first, chain, rad, var, reus, thr, guide_options=go,
+                                                 px_samples=pxs)
+                    committed = want["history"]
+                got = accumulate(pr, history, H, W, plain=plain, commit=commit)
+            what = f"view {k} ({'plain' if plain else 'specular'}, commit {commit})"
+            if plain:
+                bad = {o: int((~bits_equal(got[o], want[o])).sum()) for o in OUTPUTS}
+                bad["rgb"] = int((got["rgb"] != want["rgb"]).sum())
+                print(f"{what}: values differing from the restatement {bad}")
+                assert not any(bad.values()), what
+            else:
+                assert_outputs(got, want, None, what)
+            if k == 2:                               # the specular commit's chain planes served
+                assert (want["kind"] == 2).any() and (want["kind"] == 1).any()
+            if commit:
+                ref_hist, views = committed, views + 1
+            # (chain_guides: None, the options, unchanged by commit=False, None again)
+            assert_history(history, ref_hist, views, what)
+            t = history.times()
+            assert len(t) == 4 and all(np.isfinite(v) and v >= 0 for v in t.values()), (what, t)
+            sizes.append(history.info["bytes"])
+            held.append(history.chain_guides)
+            cam.close()
+    assert views == 3 and held == [None, {"max_bounces": 8, "max_fuzz": 0.0}, {"max_bounces": 8, "max_fuzz": 0.0}, None]
+    assert sizes[0] < sizes[1] == sizes[2] == sizes[3], sizes     # the chain planes: the first specular commit alone
 
 
 def test_without_specular_materials_the_call_and_the_history_are_the_plain_ones(rt, gpu):
