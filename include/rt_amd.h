@@ -81,7 +81,19 @@ typedef struct {
  * pointers in full-frame layout (width*height*3, row-major, RGB) and only the
  * region's tiles are written. Tiles are 8x8 pixel blocks enumerated row-major
  * over the region; this launch renders tile t iff t % tile_groups == tile_group
- * (tile_groups = 1: the whole region). `stream` is a hipStream_t (NULL = default). */
+ * (tile_groups = 1: the whole region). `stream` is a hipStream_t (NULL = default).
+ *
+ * Ordering. Calls on one camera take effect in the order they were issued, whatever stream
+ * each was queued on. Every entry but rt_camera_render_device and rt_camera_stats_words queues
+ * on the null stream and returns with its work done. A camera's device context shares its stats
+ * words, hand-out counter, record buffer and caches between all of its calls, so a call that
+ * queues on a stream other than the one the context's previous call left work on (an
+ * asynchronous launch, a stats-words copy) first makes its stream wait, on the device, for
+ * that work: a non-blocking side stream followed by a null-stream entry needs no host sync from
+ * the caller. A sequence of calls on one stream adds no wait and no host sync. Calls on
+ * different cameras are independent. The caller's output buffers are the caller's to order: an
+ * asynchronous launch's outputs are ready once `stream` has run. The camera keeps no stream
+ * handle: a stream may be destroyed once the work queued on it has run. */
 typedef struct {
     rt_region region;
     int32_t tile_group, tile_groups;
@@ -242,7 +254,10 @@ int rt_camera_kernel_times(rt_camera* cam, float* path_ms, float* accum_ms);
  * samples min (~0 = none), samples max, bounces total, bounces min (~0 = none),
  * bounces max, error flags. Multi-GPU ranks ship these beside their slab so rank
  * 0 can merge them as RenderStats.merge does (src/render-utils/renderStats.ts:
- * 42-64, called from src/raytracer.ts:86-89) without a host round trip. */
+ * 42-64, called from src/raytracer.ts:86-89) without a host round trip.
+ * Ordered like a launch (rt_launch, Ordering): on the render's own stream the copy simply
+ * follows it; on another stream it first waits for the render, and a later call on the camera
+ * that queues elsewhere waits for the copy before it resets the words. */
 #define RT_STATS_WORDS 8
 int rt_camera_stats_words(rt_camera* cam, uint64_t* dst, void* stream);
 

@@ -92,6 +92,9 @@ void DevCtx::release() {
         if (e) (void)hipEventDestroy(e), e = nullptr;
     ev.clear();
     n_passes = 0;
+    if (order_ev) (void)hipEventDestroy(order_ev);
+    order_ev = nullptr;
+    order_pending = false;
     live = false;
 }
 
@@ -200,11 +203,26 @@ const uint2* DevCtx::ensure_primary_table(hipStream_t stream) {
                                        C.n_prims, d_ptab, stream),
                   "primary_table_kernel launch");
         hip_check(hipEventRecord(ptab_ev[1], stream), "hipEventRecord");
-        ptab_stream = stream;
-    } else if (stream != ptab_stream) {
+    } else {
         hip_check(hipStreamWaitEvent(stream, ptab_ev[1], 0), "hipStreamWaitEvent");
     }
     return reinterpret_cast<const uint2*>(d_ptab.p);
+}
+
+void DevCtx::order_after(hipStream_t stream) {
+    if (order_pending && order_key != reinterpret_cast<uintptr_t>(stream))
+        hip_check(hipStreamWaitEvent(stream, order_ev, 0), "hipStreamWaitEvent");
+}
+
+void DevCtx::order_mark(hipStream_t stream, bool check) {
+    hipError_t e = hipSuccess;
+    if (!order_ev) e = hipEventCreateWithFlags(&order_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(order_ev, stream);
+    if (e == hipSuccess) {
+        order_key = reinterpret_cast<uintptr_t>(stream);
+        order_pending = true;
+    }
+    if (check) hip_check(e, "hipEventRecord(order)");
 }
 
 float DevCtx::primary_table_ms() {

@@ -133,7 +133,6 @@ struct DevCtx {
     // on first use (the camera and the primitives never change after rt_camera_create)
     DevBuf<uint64_t> d_ptab;
     hipEvent_t ptab_ev[2] = {nullptr, nullptr};  // around the builder kernel
-    hipStream_t ptab_stream = nullptr;           // the stream it was queued on
     bool ptab_used = false;                      // the last launch ran pt_pool_primary_kernel
     DevBuf<unsigned long long> d_stats, d_counters;
     DevBuf<unsigned int> d_tile;
@@ -171,8 +170,9 @@ struct DevCtx {
 
     DevScene dev_scene() const;
 
-    // The primary-ray candidate table, built on `stream` at first use; a launch on another
-    // stream waits for the builder.
+    // The primary-ray candidate table, built on `stream` at first use; every later launch makes
+    // its stream wait for the builder's end event (nothing to wait for on the builder's own stream
+    // or once it has run). No stream handle is kept: the caller may destroy its stream.
     const uint2* ensure_primary_table(hipStream_t stream);
     // Device time of the builder kernel (0 before it ran). Waits for it.
     float primary_table_ms();
@@ -323,6 +323,22 @@ struct DevCtx {
 
     void read_stats(rt_render_stats* st, uint64_t* counters, hipStream_t stream);
 
+    // ---- Ordering between calls (rt_amd.h, rt_launch) -------------------------------------------
+    // Calls on one context take effect in the order they were issued, whatever stream each queues
+    // on: they share the stats words, the hand-out counter, the record buffer and every cache
+    // above. An entry that returns with work still queued (an asynchronous rt_camera_render_device,
+    // rt_camera_stats_words) records order_ev after it; the next call that queues on another stream
+    // makes its stream wait for the event first. order_key is that stream's handle as a number: it
+    // is compared and never handed to the runtime, so the caller may destroy the stream. A call on
+    // the same stream adds no wait and no host sync.
+    hipEvent_t order_ev = nullptr;  // hipEventDisableTiming
+    uintptr_t order_key = 0;
+    bool order_pending = false;
+    // `stream` is about to queue work of this context (the context's device is current).
+    void order_after(hipStream_t stream);
+    // The call that queued on `stream` returns without a host sync. check: throw on a HIP error.
+    void order_mark(hipStream_t stream, bool check = true);
+
     // RenderStats from the 8 stats words; the reference's thrown Errors for the error flags.
     static void stats_from_words(const unsigned long long* w, rt_render_stats* st);
 };
@@ -344,11 +360,15 @@ struct rt_camera : rt::CamHost {
         ctxs.emplace_back(new rt::DevCtx(*this, dev, inst));
         return *ctxs.back();
     }
-    // the context of the calling thread's current HIP device
-    rt::DevCtx& current() {
+    // the context of the calling thread's current HIP device, for a call that queues on `stream`
+    // (every entry but rt_camera_render_device: the null stream): ordered after the context's
+    // previous call (DevCtx::order_after)
+    rt::DevCtx& current(hipStream_t stream = nullptr) {
         int dev = 0;
         rt::hip_check(hipGetDevice(&dev), "hipGetDevice");
-        return ctx(dev, 0);
+        rt::DevCtx& c = ctx(dev, 0);
+        c.order_after(stream);
+        return c;
     }
     rt::DevCtx* prog = nullptr;  // the context that holds the open progressive session
     void release() {
@@ -360,6 +380,11 @@ struct rt_camera : rt::CamHost {
     // the open session's context; a step, info or save without one is an argument error
     rt::DevCtx& session(const char* what) {
         if (!prog || !prog->prog.open) throw std::invalid_argument(std::string(what) + ": no progressive session is open");
+        if (prog->order_pending) {  // (the session entries queue on the null stream)
+            rt::DeviceScope scope;
+            rt::hip_check(hipSetDevice(prog->device), "hipSetDevice");
+            prog->order_after(nullptr);
+        }
         return *prog;
     }
     void end_session() {

@@ -165,6 +165,7 @@ DevCtx& render_multi(rt_camera* cam, const int32_t* devices, int n, const rt_reg
             c.ensure_device();
             c.ensure_multi(slab_b, rslab_b, g == 0, n);
             if (g == 0) c.ensure_frame();
+            c.order_after(c.stream);  // (the call ends with a host sync of the root's stream)
             c.launch(plan.region, g, n, cam->precision, cam->traversal, 0, c.d_slab, want_rad ? c.d_rslab.p : nullptr,
                      nullptr, nullptr, 1, c.stream);
             // the stats words into the slab's spare tile (rides in the gather)

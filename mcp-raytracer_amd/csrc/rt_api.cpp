@@ -282,17 +282,23 @@ int rt_camera_render_png(rt_camera* cam, int32_t bands, rt_render_stats* stats, 
 int rt_camera_render_device(rt_camera* cam, const rt_launch* L, rt_render_stats* stats, uint64_t* work_counters) {
     if (!cam || !L) return set_error(RT_ERR_INVALID, "null argument");
     return camera_call(cam, [&] {
-        DevCtx& c = cam->current();
-        c.ensure_device();
         const hipStream_t stream = (hipStream_t)L->stream;
+        DevCtx& c = cam->current(stream);
+        c.ensure_device();
         const int prec = L->precision < 0 ? cam->precision : L->precision;
         const int trav = L->traversal < 0 ? cam->traversal : L->traversal;
         if (L->count_work < 0 || L->count_work > 2) throw std::invalid_argument("count_work must be 0, 1 or 2");
         cam->last = &c;
         cam->multi.clear();
-        c.launch(L->region, L->tile_group, L->tile_groups, prec, trav, L->count_work, L->rgb, L->radiance,
-                 L->px_samples, L->px_bounces, L->packed_tiles, stream);
+        try {
+            c.launch(L->region, L->tile_group, L->tile_groups, prec, trav, L->count_work, L->rgb, L->radiance,
+                     L->px_samples, L->px_bounces, L->packed_tiles, stream);
+        } catch (...) {  // (what it queued before it threw is ordered like a launch)
+            c.order_mark(stream, false);
+            throw;
+        }
         if (L->synchronize) c.read_stats(stats, L->count_work ? work_counters : nullptr, stream);
+        else c.order_mark(stream);
     });
 }
 
@@ -517,10 +523,12 @@ int rt_camera_stats_words(rt_camera* cam, uint64_t* dst, void* stream) {
     try {
         DevCtx* c = cam->last;
         if (!c || !c->live || !c->d_stats) throw std::invalid_argument("rt_camera_stats_words: no render yet");
+        c->order_after((hipStream_t)stream);
         // the ST_WORDS words sit kStatStride apart (one 128-B line each); dst gets them packed
         hip_check(hipMemcpy2DAsync(dst, sizeof(uint64_t), c->d_stats, kStatStride * sizeof(unsigned long long),
                                    sizeof(uint64_t), ST_WORDS, hipMemcpyDeviceToDevice, (hipStream_t)stream),
                   "hipMemcpy2DAsync(stats)");
+        c->order_mark((hipStream_t)stream);
         return RT_OK;
     } catch (const std::invalid_argument& e) {
         return set_error(RT_ERR_INVALID, e.what());
@@ -597,7 +605,7 @@ int rt_camera_primary_table_device(rt_camera* cam, uint64_t* out, int32_t capaci
         DevCtx& c = cam->current();
         c.ensure_device();
         c.ensure_primary_table(nullptr);
-        hip_check(hipStreamSynchronize(c.ptab_stream), "hipStreamSynchronize");
+        hip_check(hipEventSynchronize(c.ptab_ev[1]), "hipEventSynchronize");
         hip_check(hipMemcpy(out, c.d_ptab, (size_t)C.width * C.height * sizeof(uint64_t), hipMemcpyDeviceToHost),
                   "hipMemcpy(primary table)");
     });
