@@ -1037,6 +1037,64 @@ int rt_camera_progressive_focus(rt_camera* cam, int32_t n_samples, const rt_focu
                                 rt_history* h, uint8_t* rgb, float* radiance, int32_t* px_samples, int32_t* px_bounces,
                                 uint8_t* selected_out, rt_render_stats* stats, rt_focus_info* info);
 
+/* ---- Sub-pixel coverage and the filters' edge hold ------------------------------------------------
+ * Opt-in and additive like the blocks above: no other call changes, RT_AMD_VERSION stays.
+ *
+ * A pixel whose footprint shows more than one surface is an anti-aliased mix, but its guides name
+ * the one surface its centre ray hits; the filters average it with that surface's neighbours and
+ * destroy the mix. On a low-noise frame of a scene with sub-pixel geometry that costs more than the
+ * filter removes. The edge hold copies exactly those pixels through unfiltered.
+ *
+ * Coverage (tests/coverage_ref.py is the definition): for every pixel of the region k x k
+ * deterministic pinhole primary rays, k in {2, 4}. Sub-ray (a, b), a, b in 0..k-1, has the offsets
+ * ox = (a + 0.5) / k - 0.5 and oy = (b + 0.5) / k - 0.5 (exact in fp32); origin = the camera's
+ * centre, direction = ((pixel00 + du i + dv j, as rt_camera_render_guides forms it) + du ox) + dv oy
+ * - centre, each vector operation in fp32; no RNG and no defocus sample whatever the camera's
+ * aperture; reference precision whatever the camera's; interval (0.001, inf); the camera's
+ * traversal. The coverage word of a pixel:
+ *   bit b k + a   the sub-ray shows the object rt_camera_render_guides reports for the pixel (the
+ *                 index in SceneData.objects; a miss is -1, and a miss equals a miss)
+ *   bits 16..23   the number of distinct objects among the sub-rays and the centre ray
+ * A pixel is MIXED when one of the low k^2 bits is clear.
+ * rt_camera_render_coverage: `coverage` is HOST width*height uint32, full-frame layout, only the
+ * region (NULL: the whole image) written; computed on the camera's device context.
+ *
+ * The hold forms of the six filter entries take one more argument and are otherwise their base
+ * entries: a held pixel takes part in every level as ever, also as a tap of its neighbours, and the
+ * last pass writes its INPUT instead - radiance_out and the u8 from the input radiance as it stands,
+ * variance_out the input variance sanitised as the filter reads it (not (v >= 0 and finite) -> 0).
+ * rt_denoise_hold / rt_denoise_variance_hold: `hold` is HOST width*height uint8, full-frame layout,
+ * non-zero = held, only the region read. The camera and session forms take hold_k: 0 = no hold
+ * (the base entry, byte for byte), 2 or 4 = the mixed pixels of that coverage, computed on the
+ * device; a session computes the mask once per hold_k and keeps it as it keeps its guides. The mask
+ * always comes from first-hit pinhole sub-rays, whatever rt_camera_set_denoise_guides selected.
+ * rt_camera_coverage_time: device time of the camera's last coverage pass (either entry kind) from
+ * HIP events; the pass runs before the span rt_camera_denoise_times reports and is not part of it.
+ * RT_ERR_INVALID, decided before any device call: k not 2 or 4, hold_k not 0, 2 or 4, a NULL
+ * coverage or hold, and whatever the base entry refuses; rt_camera_coverage_time before any pass.
+ * Limits: the mask is pinhole, so a defocus camera's blur is not in it; held pixels stay as noisy
+ * as they were; behind mirrors and glass the mask describes the specular surface, not what it
+ * shows. rt_camera_progressive_accumulate's filter, the N-API addon and multi-GPU renders have no
+ * hold form. */
+int rt_camera_render_coverage(rt_camera* cam, const rt_region* region, int32_t k, uint32_t* coverage);
+int rt_camera_coverage_time(rt_camera* cam, float* coverage_ms);
+int rt_denoise_hold(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,
+                    const float* radiance, const float* normal, const float* position, const float* distance,
+                    const int32_t* object, const uint8_t* hold, float* radiance_out, uint8_t* rgb_out);
+int rt_denoise_variance_hold(int32_t width, int32_t height, const rt_region* region,
+                             const rt_denoise_var_options* options, const float* radiance, const float* variance,
+                             const float* normal, const float* position, const float* distance, const int32_t* object,
+                             const uint8_t* hold, float* radiance_out, float* variance_out, uint8_t* rgb_out);
+int rt_camera_denoise_hold(rt_camera* cam, const rt_region* region, const rt_denoise_options* options, int32_t hold_k,
+                           const float* radiance, float* radiance_out, uint8_t* rgb_out);
+int rt_camera_denoise_variance_hold(rt_camera* cam, const rt_region* region, const rt_denoise_var_options* options,
+                                    int32_t hold_k, const float* radiance, const float* variance, float* radiance_out,
+                                    float* variance_out, uint8_t* rgb_out);
+int rt_camera_progressive_denoise_hold(rt_camera* cam, const rt_denoise_options* options, int32_t hold_k, uint8_t* rgb,
+                                       float* radiance);
+int rt_camera_progressive_denoise_variance_hold(rt_camera* cam, const rt_denoise_var_options* options, int32_t hold_k,
+                                                uint8_t* rgb, float* radiance, float* variance_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,13 +32,15 @@ static void dn_outputs(const DnBufs& b, const RegionIo& io, bool var, float* rad
 
 // The three shapes of a filter call, plain or variance-guided (o.var: `variance` in, or the
 // session's own, and `variance_out`); `o` as dn_options gives it, resolved where the entry point
-// always has. Every argument error comes before anything touches a device.
+// always has. Every argument error comes before anything touches a device. The edge hold
+// (coverage.hpp) is the frame call's `hold` mask (null: none) and the other two's hold_k (0: none),
+// whose mask the coverage pass computes on the device.
 
 // The stand-alone frame call: explicit guides, buffers of its own.
 static int dn_frame_call(const std::string& who, DnOpts o, int32_t width, int32_t height, const rt_region* region,
                          const float* radiance, const float* variance, const float* normal, const float* position,
                          const float* distance, const int32_t* object, float* radiance_out, float* variance_out,
-                         uint8_t* rgb_out) {
+                         uint8_t* rgb_out, const uint8_t* hold = nullptr) {
     return api_guard([&] {
         if (width <= 0 || height <= 0) throw std::invalid_argument(who + ": width and height must be positive");
         if (!radiance || (o.var && !variance) || !normal || !position || !distance || !object)
@@ -54,8 +56,13 @@ static int dn_frame_call(const std::string& who, DnOpts o, int32_t width, int32_
             io.up(b.var, variance, sizeof(float));
         }
         upload_guides(b, io, normal, position, distance, object);
+        DevBuf<uint8_t> d_hold;
+        if (hold) {
+            d_hold.ensure((size_t)io.n(), "hipMalloc(denoise hold)");
+            io.up(d_hold, hold, 1);
+        }
         dn_filter(b, b.gn, b.gp, b.rad(), io.r.width, 0, 0, io.r.width, io.r.height, o, radiance_out != nullptr,
-                  rgb_out != nullptr, variance_out != nullptr, io.stream, nullptr);
+                  rgb_out != nullptr, variance_out != nullptr, io.stream, nullptr, d_hold);
         dn_outputs(b, io, o.var, radiance_out, variance_out, rgb_out);
     });
 }
@@ -63,12 +70,13 @@ static int dn_frame_call(const std::string& who, DnOpts o, int32_t width, int32_
 // The camera call: the guide pass of the camera's scene over the region, the camera's buffers.
 static int dn_camera_call(rt_camera* cam, const std::string& who, DnOpts o, const rt_region* region,
                           const float* radiance, const float* variance, float* radiance_out, float* variance_out,
-                          uint8_t* rgb_out) {
+                          uint8_t* rgb_out, int32_t hold_k = 0) {
     return camera_call(cam, [&] {
         const RtCamera& C = cam->build.cam;
         if (!radiance || (o.var && !variance))
             throw std::invalid_argument(who + (o.var ? ": radiance and variance are required" : ": radiance is required"));
         o = dn_resolve(o, who);
+        hold_check(hold_k, who);
         const RegionIo io{C.width, dn_region(region, C.width, C.height, who), nullptr};
         DevCtx& c = cam->current();
         c.ensure_device();
@@ -80,25 +88,42 @@ static int dn_camera_call(rt_camera* cam, const std::string& who, DnOpts o, cons
             b.var.ensure((size_t)io.n(), "hipMalloc(denoise variance)");
             io.up(b.var, variance, sizeof(float));
         }
+        // (the coverage pass has events of its own and runs before the filter's span)
+        if (hold_k) {
+            c.d_hold.ensure((size_t)io.n(), "hipMalloc(denoise hold)");
+            c.launch_coverage_pass(io.r, cam->traversal, hold_k, nullptr, c.d_hold, io.stream);
+        }
         hip_check(hipEventRecord(ev[0], io.stream), "hipEventRecord");
         c.launch_guide_pass(io.r, cam->traversal, DenoiseGuides{b.gn, b.gp}, io.stream, &cam->dn_guide);
         c.dn_guides = true;
         dn_filter(b, b.gn, b.gp, b.rad(), io.r.width, 0, 0, io.r.width, io.r.height, o, radiance_out != nullptr,
-                  rgb_out != nullptr, variance_out != nullptr, io.stream, ev + 1);
+                  rgb_out != nullptr, variance_out != nullptr, io.stream, ev + 1, hold_k ? c.d_hold.p : nullptr);
         dn_outputs(b, io, o.var, radiance_out, variance_out, rgb_out);
     });
+}
+
+// The session's hold mask for hold_k (0: none asked for): computed once per k (queued), freed with
+// the session.
+static void session_hold(rt_camera* cam, DevCtx& c, int32_t hold_k, hipStream_t stream) {
+    DevCtx::ProgSession& P = c.prog;
+    if (!hold_k || P.hold_k == hold_k) return;
+    P.hold_k = 0;
+    P.d_hold.ensure((size_t)P.region.width * P.region.height, "hipMalloc(session hold)");
+    c.launch_coverage_pass(P.region, cam->traversal, hold_k, nullptr, P.d_hold, stream);
+    P.hold_k = hold_k;
 }
 
 // The session call: the session's device frame (and, variance-guided, its state) as they stand
 // after the last step - nothing is uploaded - and the session's guides.
 static int dn_session_call(rt_camera* cam, const std::string& who, DnOpts o, uint8_t* rgb, float* radiance,
-                           float* variance_out) {
+                           float* variance_out, int32_t hold_k = 0) {
     return camera_call(cam, [&] {
         (void)cam->session(who.c_str());
         // (the plain call names a wrong mode before its options, the variance-guided one its
         // options before the mode and the sample count)
         if (!o.var) session_radiance(cam, who);
         o = dn_resolve(o, who);
+        hold_check(hold_k, who);
         DevCtx& c = session_with(cam, who, o.var ? 2 : 0);
         const RtCamera& C = cam->build.cam;
         DevCtx::ProgSession& P = c.prog;
@@ -106,6 +131,7 @@ static int dn_session_call(rt_camera* cam, const std::string& who, DnOpts o, uin
         DnBufs& b = c.dn;
         b.ensure((size_t)io.n());
         hipEvent_t* ev = c.dn_events(o.levels);
+        session_hold(cam, c, hold_k, io.stream);
         hip_check(hipEventRecord(ev[0], io.stream), "hipEventRecord");
         // the span [0, 1): the guide pass of a first call (through the specular chain: of the first
         // call with these options) and, variance-guided, the variance pass
@@ -118,7 +144,7 @@ static int dn_session_call(rt_camera* cam, const std::string& who, DnOpts o, uin
         const float4 *gn = spec ? P.d_sgn : P.d_gn, *gp = spec ? P.d_sgp : P.d_gp;
         if (o.var) prog_variance_pass(c, io.stream);
         dn_filter(b, gn, gp, P.d_rad, C.width, io.r.x, io.r.y, io.r.width, io.r.height, o, radiance != nullptr,
-                  rgb != nullptr, variance_out != nullptr, io.stream, ev + 1);
+                  rgb != nullptr, variance_out != nullptr, io.stream, ev + 1, hold_k ? P.d_hold.p : nullptr);
         dn_outputs(b, io, o.var, radiance, variance_out, rgb);
     });
 }
@@ -222,6 +248,78 @@ int rt_camera_progressive_variance(rt_camera* cam, float* variance) {
         prog_variance_pass(c, io.stream);
         io.down(variance, c.dn.var, sizeof(float));
         hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_camera_render_coverage(rt_camera* cam, const rt_region* region, int32_t k, uint32_t* coverage) {
+    return camera_call(cam, [&] {
+        const std::string who = "rt_camera_render_coverage";
+        if (k != 2 && k != 4) throw std::invalid_argument(who + ": k must be 2 or 4");
+        if (!coverage) throw std::invalid_argument(who + ": coverage is required");
+        const RtCamera& C = cam->build.cam;
+        const RegionIo io{C.width, dn_region(region, C.width, C.height, who), nullptr};
+        DevCtx& c = cam->current();
+        c.ensure_device();
+        c.d_cov.ensure((size_t)io.n(), "hipMalloc(coverage)");
+        c.launch_coverage_pass(io.r, cam->traversal, k, c.d_cov, nullptr, io.stream);
+        io.down(coverage, c.d_cov, sizeof(uint32_t));
+        hip_check(hipStreamSynchronize(io.stream), "hipStreamSynchronize");
+    });
+}
+
+int rt_denoise_hold(int32_t width, int32_t height, const rt_region* region, const rt_denoise_options* options,
+                    const float* radiance, const float* normal, const float* position, const float* distance,
+                    const int32_t* object, const uint8_t* hold, float* radiance_out, uint8_t* rgb_out) {
+    if (!hold) return set_error(RT_ERR_INVALID, "rt_denoise_hold: hold is required");
+    return dn_frame_call("rt_denoise_hold", dn_options(options), width, height, region, radiance, nullptr, normal,
+                         position, distance, object, radiance_out, nullptr, rgb_out, hold);
+}
+
+int rt_denoise_variance_hold(int32_t width, int32_t height, const rt_region* region,
+                             const rt_denoise_var_options* options, const float* radiance, const float* variance,
+                             const float* normal, const float* position, const float* distance, const int32_t* object,
+                             const uint8_t* hold, float* radiance_out, float* variance_out, uint8_t* rgb_out) {
+    if (!hold) return set_error(RT_ERR_INVALID, "rt_denoise_variance_hold: hold is required");
+    return dn_frame_call("rt_denoise_variance_hold", dn_options(options), width, height, region, radiance, variance,
+                         normal, position, distance, object, radiance_out, variance_out, rgb_out, hold);
+}
+
+int rt_camera_denoise_hold(rt_camera* cam, const rt_region* region, const rt_denoise_options* options, int32_t hold_k,
+                           const float* radiance, float* radiance_out, uint8_t* rgb_out) {
+    return dn_camera_call(cam, "rt_camera_denoise_hold", dn_options(options), region, radiance, nullptr, radiance_out,
+                          nullptr, rgb_out, hold_k);
+}
+
+int rt_camera_denoise_variance_hold(rt_camera* cam, const rt_region* region, const rt_denoise_var_options* options,
+                                    int32_t hold_k, const float* radiance, const float* variance, float* radiance_out,
+                                    float* variance_out, uint8_t* rgb_out) {
+    return dn_camera_call(cam, "rt_camera_denoise_variance_hold", dn_options(options), region, radiance, variance,
+                          radiance_out, variance_out, rgb_out, hold_k);
+}
+
+int rt_camera_progressive_denoise_hold(rt_camera* cam, const rt_denoise_options* options, int32_t hold_k, uint8_t* rgb,
+                                       float* radiance) {
+    return dn_session_call(cam, "rt_camera_progressive_denoise_hold", dn_options(options), rgb, radiance, nullptr,
+                           hold_k);
+}
+
+int rt_camera_progressive_denoise_variance_hold(rt_camera* cam, const rt_denoise_var_options* options, int32_t hold_k,
+                                                uint8_t* rgb, float* radiance, float* variance_out) {
+    return dn_session_call(cam, "rt_camera_progressive_denoise_variance_hold", dn_options(options), rgb, radiance,
+                           variance_out, hold_k);
+}
+
+int rt_camera_coverage_time(rt_camera* cam, float* coverage_ms) {
+    if (!coverage_ms) return set_error(RT_ERR_INVALID, "null argument");
+    return camera_call(cam, [&] {
+        DevCtx* c = nullptr;
+        for (auto& x : cam->ctxs)
+            if (x->cov_timed) c = x.get();
+        if (!c) throw std::invalid_argument("rt_camera_coverage_time: no coverage pass yet");
+        DeviceScope scope;
+        hip_check(hipSetDevice(c->device), "hipSetDevice");
+        hip_check(hipEventSynchronize(c->cov_ev[1]), "hipEventSynchronize");
+        hip_check(hipEventElapsedTime(coverage_ms, c->cov_ev[0], c->cov_ev[1]), "hipEventElapsedTime");
     });
 }
 

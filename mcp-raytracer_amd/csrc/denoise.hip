@@ -130,11 +130,24 @@ __global__ __launch_bounds__(kDnBlock) void denoise_pack_kernel(const float* rad
     fn[k] = make_float4(a.x, a.y, a.z, 1.0f / (sigma_plane * a.w));
 }
 
+// hd.mask (or null): a held pixel's outputs are the filter's INPUTS, read again where the pack pass
+// read them - the colour as it stands, the variance sanitised as there. Each thread reads its own
+// pixel's inputs before it writes, so the outputs may be the input arrays themselves.
 __global__ __launch_bounds__(kDnBlock) void denoise_unpack_kernel(const float4* colour, int n, float* rad, uint8_t* rgb,
-                                                                   float* variance) {
+                                                                   float* variance, DenoiseHold hd) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const float4 c = colour[k];
+    float4 c = colour[k];
+    if (hd.mask && hd.mask[k]) {
+        const int y = k / hd.w, x = k - y * hd.w;
+        const float* s = hd.rad + 3 * ((size_t)(hd.y0 + y) * (size_t)hd.pitch_px + (size_t)(hd.x0 + x));
+        float vs = 0.0f;
+        if (hd.variance) {
+            const float v = hd.variance[k];
+            vs = v >= 0.0f && finite_f(v) ? v : 0.0f;
+        }
+        c = make_float4(s[0], s[1], s[2], vs);
+    }
     if (variance) variance[k] = dn_var(c);
     if (rad) {
         rad[3 * (size_t)k] = c.x;
@@ -404,9 +417,10 @@ hipError_t launch_denoise_level(bool var, const float4* src, float4* dst, const 
 }
 
 hipError_t launch_denoise_unpack(const float4* colour, int n, float* rad, uint8_t* rgb, float* variance,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, const DenoiseHold& hold) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(denoise_unpack_kernel, grid1(n), dim3(kDnBlock), 0, stream, colour, n, rad, rgb, variance);
+    if (hold.mask && (hold.w <= 0 || !hold.rad)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(denoise_unpack_kernel, grid1(n), dim3(kDnBlock), 0, stream, colour, n, rad, rgb, variance, hold);
     return hipGetLastError();
 }
 

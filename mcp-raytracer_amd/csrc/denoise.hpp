@@ -68,9 +68,21 @@ hipError_t launch_denoise_pack(const float* rad, int pitch_px, int x0, int y0, i
 // Steps 1 and 2 stage a 16x16 tile plus halo in LDS; larger steps read global memory.
 hipError_t launch_denoise_level(bool var, const float4* src, float4* dst, const float4* fn, const float4* gp, int w,
                                 int h, int step, float ks, hipStream_t stream);
+// The edge hold (coverage.hpp): pixels the filter's unpack pass copies through. mask: region-packed,
+// non-zero = held (null: none). A held pixel took part in every level as ever, taps included; its
+// outputs are the filter's inputs as launch_denoise_pack read them: `rad` / pitch_px / x0 / y0 and
+// the region's width w, and `variance` (region-packed, sanitised as there; null: the plain form).
+struct DenoiseHold {
+    const uint8_t* mask = nullptr;
+    const float* rad = nullptr;
+    int pitch_px = 0, x0 = 0, y0 = 0, w = 0;
+    const float* variance = nullptr;
+};
+
 // colour -> region-packed float[3] radiance and / or its u8 (the frame's own to_u8) and / or,
-// after the variance-guided form, the filtered variance (the flag bit cleared).
+// after the variance-guided form, the filtered variance (the flag bit cleared). hold: above; its
+// inputs may be the very arrays `rad` and `variance` name.
 hipError_t launch_denoise_unpack(const float4* colour, int n, float* rad, uint8_t* rgb, float* variance,
-                                 hipStream_t stream);
+                                 hipStream_t stream, const DenoiseHold& hold = DenoiseHold{});
 
 }  // namespace rt

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <stdexcept>
 
+#include "coverage.hpp"
 #include "pass_host.hpp"
 #include "prog_blob.hpp"
 
@@ -75,6 +76,11 @@ void DevCtx::release() {
         if (e) (void)hipEventDestroy(e), e = nullptr;
     dn_ev.clear();
     dn_levels = 0;
+    d_cov.reset();
+    d_hold.reset();
+    for (hipEvent_t& e : cov_ev)
+        if (e) (void)hipEventDestroy(e), e = nullptr;
+    cov_timed = false;
     rp_prev.free();
     d_reusable.reset();
     for (hipEvent_t& e : rp_ev)
@@ -547,8 +553,7 @@ hipEvent_t* DevCtx::dn_events(int levels) {
     return dn_ev.data();
 }
 
-void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream,
-                               const rt_guide_options* go, int32_t* chain) {
+int DevCtx::first_hit_traversal(int trav) {
     const RtCamera& C = build.cam;
     if (!d_prim_object) {
         std::vector<int32_t> po(std::max<size_t>(C.n_prims, 1), -1);
@@ -560,6 +565,25 @@ void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides
     const int tr = effective_traversal(trav);
     if (stack_lds_bytes(C.stack_depth, tr, C.n_prims) > (size_t)lds_max)
         throw std::runtime_error("traversal stack exceeds the workgroup LDS (BVH too deep)");
+    return tr;
+}
+
+void DevCtx::launch_coverage_pass(const rt_region& r, int trav, int k, uint32_t* coverage, uint8_t* hold,
+                                  hipStream_t stream) {
+    const int tr = first_hit_traversal(trav);
+    for (hipEvent_t& e : cov_ev)
+        if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+    hip_check(hipEventRecord(cov_ev[0], stream), "hipEventRecord");
+    hip_check(launch_coverage(dev_scene(), tr, RtRegion{r.x, r.y, r.width, r.height, 0, 1}, d_prim_object, k, coverage,
+                              hold, lds_max, stream),
+              "coverage_kernel launch");
+    hip_check(hipEventRecord(cov_ev[1], stream), "hipEventRecord");
+    cov_timed = true;
+}
+
+void DevCtx::launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream,
+                               const rt_guide_options* go, int32_t* chain) {
+    const int tr = first_hit_traversal(trav);
     const RtRegion reg{r.x, r.y, r.width, r.height, 0, 1};
     if (go && go->mode == RT_GUIDES_SPECULAR) {
         hip_check(launch_guide_walk(dev_scene(), tr, reg, d_prim_object, g, chain, go->max_bounces, go->max_fuzz, lds_max,

@@ -217,6 +217,10 @@ struct DevCtx {
         // the region's guides through the specular chain (guide_walk.hip), of the options sg_key:
         // a pair of their own - reprojection, accumulation and focus read d_gn / d_gp
         DevBuf<float4> d_sgn, d_sgp;
+        // the region's edge-hold mask (coverage.hpp) for hold_k sub-rays a side (0: none yet),
+        // computed by the first rt_camera_progressive_denoise*_hold call that asks for that k
+        DevBuf<uint8_t> d_hold;
+        int32_t hold_k = 0;
         rt_guide_options sg_key{};
         bool sg_valid = false;
         // the chain plane of that walk, kept once a reprojection through the chains asked for it
@@ -269,6 +273,20 @@ struct DevCtx {
     // null) receives either pass's chain word.
     void launch_guide_pass(const rt_region& r, int trav, const DenoiseGuides& g, hipStream_t stream,
                            const rt_guide_options* go = nullptr, int32_t* chain = nullptr);
+
+    // What the first-hit passes share: d_prim_object uploaded once, and the strategy `trav` resolves
+    // to, whose traversal stack must fit the workgroup's LDS.
+    int first_hit_traversal(int trav);
+
+    // ---- Sub-pixel coverage (coverage.hpp) -------------------------------------------------------
+    DevBuf<uint32_t> d_cov;   // one call's coverage words (region-packed, kept between calls)
+    DevBuf<uint8_t> d_hold;   // a camera filter call's hold mask (a session keeps its own)
+    // HIP events around the last coverage pass of this context
+    hipEvent_t cov_ev[2] = {nullptr, nullptr};
+    bool cov_timed = false;
+    // The coverage pass over `r` (clamped) for k x k sub-rays into coverage / hold (region-packed,
+    // either may be null), through the strategy `trav` resolves to, between cov_ev; queued.
+    void launch_coverage_pass(const rt_region& r, int trav, int k, uint32_t* coverage, uint8_t* hold, hipStream_t stream);
 
     // ---- Reprojection (reproject.hpp) -----------------------------------------------------------
     // As the NEW view's context: the reusable table and the events of the last call. As the

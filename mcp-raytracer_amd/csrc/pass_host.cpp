@@ -214,8 +214,13 @@ void prog_copy_out(const DevCtx& c, void* host, const void* dev, size_t elem, hi
               "hipMemcpy2DAsync");
 }
 
+void hold_check(int32_t hold_k, const std::string& who) {
+    if (hold_k != 0 && hold_k != 2 && hold_k != 4) throw std::invalid_argument(who + ": hold_k must be 0, 2 or 4");
+}
+
 void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0, int w,
-               int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream, hipEvent_t* ev) {
+               int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream, hipEvent_t* ev,
+               const uint8_t* hold) {
     int e = 0;
     auto mark = [&] {
         if (ev) hip_check(hipEventRecord(ev[e++], stream), "hipEventRecord");
@@ -236,7 +241,8 @@ void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, 
         std::swap(src, dst);
     }
     hip_check(launch_denoise_unpack(src, w * h, want_rad ? b.rad() : nullptr, want_u8 ? b.u8.p : nullptr,
-                                    o.var && want_var ? b.var.p : nullptr, stream),
+                                    o.var && want_var ? b.var.p : nullptr, stream,
+                                    DenoiseHold{hold, rad, pitch_px, x0, y0, w, o.var ? b.var.p : nullptr}),
               "denoise_unpack_kernel");
     mark();
 }

@@ -115,9 +115,13 @@ void prog_copy_out(const DevCtx& c, void* host, const void* dev, size_t elem, hi
 // launch per level over the ping-pong pair, then the result into b.rad() / b.u8 and, when
 // want_var, the filtered variance into b.var (region-packed). `o` is resolved. ev (or null):
 // levels + 3 events, recorded before the pack pass, after it, after every level and after the
-// unpack pass. Queued.
+// unpack pass. hold (region-packed, or null): the pixels the unpack pass copies through from `rad`
+// and b.var (DenoiseHold). Queued.
 void dn_filter(DnBufs& b, const float4* gn, const float4* gp, const float* rad, int pitch_px, int x0, int y0, int w,
-               int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream, hipEvent_t* ev);
+               int h, const DnOpts& o, bool want_rad, bool want_u8, bool want_var, hipStream_t stream, hipEvent_t* ev,
+               const uint8_t* hold = nullptr);
+// hold_k of a camera or session filter call: 0 (no hold), 2 or 4, else an argument error.
+void hold_check(int32_t hold_k, const std::string& who);
 
 inline RpView rp_camera_view(const rt_camera* cam) {
     const RtCamera& C = cam->build.cam;

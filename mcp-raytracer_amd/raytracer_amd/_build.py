@@ -57,6 +57,9 @@ _UNITS = [
     # the guides through the specular chain: the same rule - the output equals
     # tests/guide_walk_ref.py in every bit
     ("guide_walk.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
+    # the sub-pixel coverage pass: denoise.hip's flags, its sub-ray directions are fp32 vector
+    # arithmetic that rounds once per operation - the words equal tests/coverage_ref.py in every bit
+    ("coverage.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
     # the reprojection gather: as the filter, every fp32 operation rounds once - the output equals
     # tests/reproject_ref.py in every bit
     ("reproject.hip", ["-ffp-contract=off", *_KERNEL_FLAGS], True),
@@ -106,7 +109,7 @@ _UNITS = [
 ]
 _HEADERS = ["json.hpp", "rt_math.hpp", "scene_types.hpp", "scene.hpp", "scene_js.hpp", "scene_tree.hpp", "pt_types.hpp", "pt_prof.hpp", "pt_num.hpp", "pt_isect.hpp", "pt_walk.hpp",
             "pt_brute.hpp", "pt_shade.hpp", "pt_pixel.hpp", "pt_kernels.hpp", "pt_pool.hpp", "pt_dispatch.hpp",
-            "launch.hpp", "progressive.hpp", "denoise.hpp",
+            "launch.hpp", "progressive.hpp", "denoise.hpp", "coverage.hpp",
             "reproject.hpp", "reproject_spec.hpp", "temporal.hpp", "temporal_spec.hpp", "gather.hpp", "focus.hpp", "png_deflate.hpp", "primary.hpp", "host_util.hpp", "scene_blob.hpp", "launch_plan.hpp", "prog_blob.hpp",
             "dev_ctx.hpp", "api_call.hpp", "pass_host.hpp"]
 _LIBS = ["-lz"]

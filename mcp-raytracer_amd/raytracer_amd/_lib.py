@@ -274,6 +274,22 @@ _SIGS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_camera_progressive_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseVarOptions), C.c_void_p,
                                                          C.c_void_p, C.c_void_p]),
+    "rt_camera_render_coverage": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.c_int32, C.c_void_p]),
+    "rt_camera_coverage_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rt_denoise_hold": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.POINTER(RtDenoiseOptions), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_variance_hold": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.POINTER(RtDenoiseVarOptions),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_denoise_hold": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.POINTER(RtDenoiseOptions), C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_denoise_variance_hold": (C.c_int, [C.c_void_p, C.POINTER(RtRegion), C.POINTER(RtDenoiseVarOptions),
+                                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "rt_camera_progressive_denoise_hold": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseOptions), C.c_int32, C.c_void_p,
+                                                     C.c_void_p]),
+    "rt_camera_progressive_denoise_variance_hold": (C.c_int, [C.c_void_p, C.POINTER(RtDenoiseVarOptions), C.c_int32,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_camera_get_view": (C.c_int, [C.c_void_p, C.POINTER(RtView)]),
     "rt_camera_reusable_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "rt_reproject": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(RtRegion), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -13,7 +13,8 @@ from dataclasses import dataclass, field
 from typing import Iterable, Optional, Sequence
 
 from . import _lib
-from .passes import (_as_frame, _denoise_out, _f32_frame, _f32_outs, _gather_options, _guide_options, _host_ptr,
+from .passes import (_as_frame, _denoise_out, _f32_frame, _f32_outs, _gather_options, _guide_options, _hold_entry,
+                     _host_ptr,
                      _region, _region_ptr, _reproject_frames, _reproject_options, _session_frame, _session_result,
                      _temporal_options, _var_call, _var_out, _view_dict)
 from .passes import _c_view  # noqa: F401  (callers that imported it from this module still find it)
@@ -400,12 +401,42 @@ class Camera:
                                                          g["object"].ctypes.data))
         return g
 
+    def render_coverage(self, region=None, k: int = 2) -> dict:
+        """Sub-pixel coverage (rt_camera_render_coverage): k x k deterministic pinhole primary rays
+        per pixel of `region` (default: the whole image), k 2 or 4, compared with the pixel's own
+        centre ray - the one render_guides traces. Returns full-frame arrays {"agree": uint16
+        (H, W), bit b*k + a set when sub-ray (a, b) shows the centre ray's object (a miss equals a
+        miss), "objects": uint8 (H, W), the number of distinct objects among the sub-rays and the
+        centre, "mixed": bool (H, W), a bit of the low k*k is clear}; pixels outside the region
+        hold zeros (not mixed). Pinhole rays whatever the camera's aperture, reference precision
+        whatever its precision. Equals tests/coverage_ref.py in every bit."""
+        import numpy as np
+        H, W = self.image_height, self.image_width
+        words = np.zeros((H, W), np.uint32)
+        _lib.check(self._lib.rt_camera_render_coverage(self._h, _region_ptr(region), int(k), words.ctypes.data))
+        full = np.uint32((1 << (int(k) * int(k))) - 1)
+        inside = np.zeros((H, W), bool)
+        if region is None:
+            inside[:] = True
+        else:
+            r = _region(region)
+            inside[max(r.y, 0):max(r.y + r.height, 0), max(r.x, 0):max(r.x + r.width, 0)] = True
+        return {"agree": (words & np.uint32(0xffff)).astype(np.uint16), "objects": ((words >> 16) & 0xff).astype(np.uint8),
+                "mixed": inside & ((words & full) != full)}
+
+    def coverage_time(self) -> float:
+        """Device time in ms of the camera's last coverage pass - render_coverage, or the first
+        hold_edges call of a frame or session (rt_camera_coverage_time), from HIP events."""
+        ms = C.c_float()
+        _lib.check(self._lib.rt_camera_coverage_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def _set_denoise_guides(self, guides) -> None:
         opts = _guide_options(guides)
         _lib.check(self._lib.rt_camera_set_denoise_guides(self._h, C.byref(opts)))
 
     def denoise(self, radiance, region=None, *, levels=4, sigma_color=None, sigma_plane=0.01, rgb=None, out=None,
-                variance=None, sigma_variance=2.0, variance_out=None, guides="first_hit"):
+                variance=None, sigma_variance=2.0, variance_out=None, guides="first_hit", hold_edges=0):
         """rt_camera_denoise: the a-trous filter of a frame of this camera (float32 (H, W, 3), as
         render_region's `radiance`), its guides computed on the device. Returns the filtered
         radiance (H, W, 3) - a new array, or `out` (which may be `radiance` itself); `rgb`
@@ -414,7 +445,12 @@ class Camera:
         and `variance_out` select the variance-guided filter (rt_camera_denoise_variance) as in
         denoise(). `guides` selects the guides the call computes (rt_camera_set_denoise_guides):
         "first_hit", "specular" - those of render_guides(through_specular=True) - or a dict of
-        max_bounces / max_fuzz for the latter."""
+        max_bounces / max_fuzz for the latter. `hold_edges` (0, 2 or 4; rt_camera_denoise_hold,
+        rt_camera_denoise_variance_hold) copies the pixels render_coverage(region, k=hold_edges)
+        calls mixed through unfiltered - colour, u8 and variance_out are their inputs - while they
+        still serve as taps: the switch that makes the filter safe on sky-lit scenes with sub-pixel
+        geometry, at the price of still-noisy edge pixels indoors. The mask is always first-hit and
+        pinhole, whatever `guides` is. 0 is the call without it, byte for byte."""
         H, W = self.image_height, self.image_width
         self._set_denoise_guides(guides)
         rad = _f32_frame(radiance, (H, W, 3), "radiance")
@@ -424,12 +460,12 @@ class Camera:
         guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
         if guided:
             var = _f32_frame(variance, (H, W), "variance")
-            _lib.check(self._lib.rt_camera_denoise_variance(self._h, rptr, C.byref(opts), rad.ctypes.data,
-                                                            var.ctypes.data, res.ctypes.data,
-                                                            _var_out(variance_out, (H, W)), uptr))
+            fn, *hold = _hold_entry(self._lib, "rt_camera_denoise_variance", hold_edges)
+            _lib.check(fn(self._h, rptr, C.byref(opts), *hold, rad.ctypes.data, var.ctypes.data, res.ctypes.data,
+                          _var_out(variance_out, (H, W)), uptr))
         else:
-            _lib.check(self._lib.rt_camera_denoise(self._h, rptr, C.byref(opts), rad.ctypes.data, res.ctypes.data,
-                                                   uptr))
+            fn, *hold = _hold_entry(self._lib, "rt_camera_denoise", hold_edges)
+            _lib.check(fn(self._h, rptr, C.byref(opts), *hold, rad.ctypes.data, res.ctypes.data, uptr))
         return _as_frame(res, H, W)
 
     def denoise_times(self) -> dict:
@@ -659,7 +695,7 @@ class ProgressiveRender:
         return out if out.shape == shape else out.reshape(shape)
 
     def denoised(self, buffer=None, radiance=None, *, levels=4, sigma_color=None, sigma_plane=0.01, variance=False,
-                 sigma_variance=2.0, variance_out=None, guides="first_hit"):
+                 sigma_variance=2.0, variance_out=None, guides="first_hit", hold_edges=0):
         """The session's frame as it stands after the last step, through the a-trous filter
         (rt_camera_progressive_denoise): the frame never leaves the device, the region's guides
         are computed on first use and kept, and the session itself is not touched. `buffer` (u8
@@ -671,7 +707,10 @@ class ProgressiveRender:
         in place of sigma_color; `variance_out` (optional float32 (H, W)) receives the region's
         filtered variance. `guides` as in Camera.denoise: the session keeps its specular guides
         beside the first-hit ones (which reprojected / accumulate / focus always use) and
-        recomputes them when max_bounces or max_fuzz change."""
+        recomputes them when max_bounces or max_fuzz change. `hold_edges` (0, 2 or 4) as in
+        Camera.denoise (rt_camera_progressive_denoise_hold, ..._variance_hold): the session computes
+        the mask of its region once per value and keeps it; held pixels come back as the session's
+        frame (and its state's variance) has them. accumulated(filter_levels=) has no hold."""
         if self._cam is None:
             raise ValueError("the progressive session is closed")
         cam = self._cam
@@ -680,9 +719,11 @@ class ProgressiveRender:
         guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
         if guided:
             vptr = _var_out(variance_out, (cam.image_height, cam.image_width))
-            _lib.check(cam._lib.rt_camera_progressive_denoise_variance(cam._h, C.byref(opts), ptr, rptr, vptr))
+            fn, *hold = _hold_entry(cam._lib, "rt_camera_progressive_denoise_variance", hold_edges)
+            _lib.check(fn(cam._h, C.byref(opts), *hold, ptr, rptr, vptr))
         else:
-            _lib.check(cam._lib.rt_camera_progressive_denoise(cam._h, C.byref(opts), ptr, rptr))
+            fn, *hold = _hold_entry(cam._lib, "rt_camera_progressive_denoise", hold_edges)
+            _lib.check(fn(cam._h, C.byref(opts), *hold, ptr, rptr))
         return _session_result(cam, radiance)
 
     def reprojected(self, prev_cam: Camera, prev_radiance, rgb=None, radiance=None, weight_out=None, *,

@@ -80,6 +80,14 @@ def _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma
     return True, _lib.RtDenoiseVarOptions(int(levels), float(sigma_variance), float(sigma_plane))
 
 
+def _hold_entry(lib, name, hold_edges):
+    """The entry a camera or session filter call runs and the argument the hold form adds after
+    its options: [lib.<name>] without hold_edges (0), else [lib.<name>_hold, hold_k] - the library
+    refuses values other than 2 and 4."""
+    k = int(hold_edges)
+    return [getattr(lib, name)] if k == 0 else [getattr(lib, name + "_hold"), k]
+
+
 def _guide_options(guides) -> _lib.RtGuideOptions:
     """rt_guide_options of a `guides=` keyword: "first_hit", "specular" (max_bounces 8, max_fuzz 0)
     or a dict of max_bounces / max_fuzz for the specular walk (the library validates the values)."""
@@ -224,7 +232,8 @@ def _session_result(cam, radiance):
 
 
 def denoise(radiance, normal, position, distance, object, region=None, *, levels=4, sigma_color=None,
-            sigma_plane=0.01, rgb=None, out=None, variance=None, sigma_variance=2.0, variance_out=None, chain=None):
+            sigma_plane=0.01, rgb=None, out=None, variance=None, sigma_variance=2.0, variance_out=None, chain=None,
+            hold=None):
     """rt_denoise: the guided edge-avoiding a-trous filter of a frame with explicit guides (as
     Camera.render_guides returns them), no camera. radiance / normal / position: float32
     (H, W, 3); distance float32, object int32: (H, W). Returns the filtered radiance (H, W, 3) -
@@ -237,7 +246,12 @@ def denoise(radiance, normal, position, distance, object, region=None, *, levels
     (rt_denoise_variance, tests/denoise_var_ref.py) with `sigma_variance` in place of
     sigma_color; `variance_out` (optional float32 (H, W)) then receives the region's filtered
     variance. Passing sigma_color together with variance raises ValueError. `chain` is accepted
-    and ignored, so denoise(radiance, **cam.render_guides(through_specular=True)) works."""
+    and ignored, so denoise(radiance, **cam.render_guides(through_specular=True)) works.
+
+    `hold` (uint8 or bool (H, W), e.g. cam.render_coverage()["mixed"]; rt_denoise_hold,
+    rt_denoise_variance_hold) marks pixels the filter copies through: they serve as taps as ever,
+    and their colour, u8 and variance_out are their inputs (the variance sanitised: negative and
+    non-finite values are 0)."""
     import numpy as np
     rad = np.asarray(radiance)
     if rad.ndim != 3 or rad.shape[2] != 3:
@@ -249,14 +263,19 @@ def denoise(radiance, normal, position, distance, object, region=None, *, levels
     uptr, _k = _host_ptr(rgb, H * W * 3, "rgb")
     rptr = _region_ptr(region)
     guided, opts = _var_call(variance, sigma_color, sigma_variance, variance_out, levels, sigma_plane)
+    mask = None if hold is None else np.ascontiguousarray(hold, dtype=np.uint8)
+    if mask is not None and mask.size != H * W:
+        raise ValueError(f"hold must hold {H}x{W} values, not {mask.size}")
+    held = [] if mask is None else [mask.ctypes.data]
+    lib, suffix = _lib.load(), "" if mask is None else "_hold"
     if guided:
         var = _f32_frame(variance, (H, W), "variance")
-        _lib.check(_lib.load().rt_denoise_variance(W, H, rptr, C.byref(opts), rad.ctypes.data, var.ctypes.data,
-                                                   *[a.ctypes.data for a in g], res.ctypes.data,
-                                                   _var_out(variance_out, (H, W)), uptr))
+        _lib.check(getattr(lib, "rt_denoise_variance" + suffix)(
+            W, H, rptr, C.byref(opts), rad.ctypes.data, var.ctypes.data, *[a.ctypes.data for a in g], *held,
+            res.ctypes.data, _var_out(variance_out, (H, W)), uptr))
     else:
-        _lib.check(_lib.load().rt_denoise(W, H, rptr, C.byref(opts), rad.ctypes.data, *[a.ctypes.data for a in g],
-                                          res.ctypes.data, uptr))
+        _lib.check(getattr(lib, "rt_denoise" + suffix)(W, H, rptr, C.byref(opts), rad.ctypes.data,
+                                                       *[a.ctypes.data for a in g], *held, res.ctypes.data, uptr))
     return _as_frame(res, H, W)
 
 
